@@ -14,6 +14,14 @@ profiles/r03n_step_sweep.txt: 768 x 4 34.8-35.0k pairs/s, 768 x 6 35.7-36.5k, 76
 768 x 3 and 384 x 3, profiles/r02m_streamsweep.txt).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B] [--streams S] [--iters I]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value,
+ms_per_step, the configuration and the cheap checks of the timed records).  --full adds what
+takes runs of its own: the serial HIP-event pass (per-kernel times, rooflines), the CPU
+baseline and the oracle parity checks, the single-pair latency, the harder and the worst-case
+batch, and at N > 1 rank 0's check of the gathered records.  --dump-outputs DIR writes the
+result records of the last timed step as DIR/<field>.npy (either mode).
 
 N > 1: launched by torch.distributed.run, one rank per GPU; each rank runs its own B pairs
 (weak scaling, independent pairs = the reference's per-pair process) and the per-pair result
@@ -62,6 +70,14 @@ def parse():
                     help="pairs workload: fraction of left keypoints with a true partner")
     ap.add_argument("--sigma", type=float, default=0.03,
                     help="pairs workload: descriptor noise of the true partners")
+    ap.add_argument("--full", action="store_true",
+                    help="pairs workload: also run everything beside the headline (serial "
+                         "HIP-event pass and rooflines, CPU baseline and oracle parity, "
+                         "single-pair latency, hard and worst-case batches, multi-rank check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="pairs workload: after the timed steps write the result records of the "
+                         "last timed step (what a caller of the timed path receives) as "
+                         "DIR/<field>.npy, float32 / float64, one row per pair")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--main-batch", choices=["default", "worst"], default="default",
                     help="pairs workload: 'worst' makes the timed batch itself the worst-case "
@@ -111,9 +127,18 @@ def parse():
 def make_batch(rank: int, B: int, kpts: int, seed: int, inlier_frac: float = 0.8,
                sigma: float = 0.03, mismatch_frac: float = 0.0):
     from erp_match_eightpoint_test_amd import synth
-    pairs = [synth.make_pair(seed + 1000 * rank + i, n_kpts=kpts, inlier_frac=inlier_frac,
-                             sigma=sigma, mismatch_frac=mismatch_frac) for i in range(B)]
-    return pairs
+    return _map_pairs(lambda i: synth.make_pair(seed + 1000 * rank + i, n_kpts=kpts,
+                                                inlier_frac=inlier_frac, sigma=sigma,
+                                                mismatch_frac=mismatch_frac), B)
+
+
+def _map_pairs(make, B: int):
+    """[make(0), ..., make(B - 1)] on a few host threads.  Only part of make_pair runs without
+    the GIL (the generators' fills and the large array operations), so the gain is a few times,
+    not the thread count.  Every pair has its own seed, so the batch is the serial one's."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(8, host_cpu_share()[0]))) as ex:
+        return list(ex.map(make, range(B)))
 
 
 def make_worst_batch(rank: int, B: int, kpts: int, sigma: float):
@@ -121,8 +146,8 @@ def make_worst_batch(rank: int, B: int, kpts: int, sigma: float):
     both valid) at inlier fraction 0.98"""
     from erp_match_eightpoint_test_amd import synth
     seeds = json.load(open(os.path.join(ROOT, "scripts", "twin_seeds.json")))["seeds"]
-    return [synth.make_pair(seeds[(rank * B + i) % len(seeds)], n_kpts=kpts, inlier_frac=0.98,
-                            sigma=sigma) for i in range(B)]
+    return _map_pairs(lambda i: synth.make_pair(seeds[(rank * B + i) % len(seeds)], n_kpts=kpts,
+                                                inlier_frac=0.98, sigma=sigma), B)
 
 
 def to_device(pairs, dev):
@@ -301,6 +326,22 @@ def parity_check(gpu_res, gpu_matches, ora):
             "fields": "status, M, K equal; min_idx equal (or, listed in r1r2_order_swaps, the "
                       "other rotation of the SAME iteration with the same R); R, T within 1e-6; "
                       "matches bit-exact"}
+
+
+def dump_outputs(out_dir, records):
+    """--dump-outputs: the erp_pair_result records a caller of the timed path receives ([pairs,
+    64] bytes, all ranks' at N > 1), one DIR/<field>.npy per result field and one row per pair:
+    R and T as the float32 they are, min_dist float64, the integer fields (exact) as float64.
+    survivors and binned_rows are left out: they count the work a launch did, not its answer."""
+    from erp_match_eightpoint_test_amd import results_to_numpy
+    res = results_to_numpy(records)
+    os.makedirs(out_dir, exist_ok=True)
+    for f in res.dtype.names:
+        if f in ("survivors", "binned_rows"):
+            continue
+        a = res[f]
+        np.save(os.path.join(out_dir, f + ".npy"),
+                np.ascontiguousarray(a if a.dtype == np.float32 else a.astype(np.float64)))
 
 
 def load_pmc(tag, stage):
@@ -631,6 +672,8 @@ def main():
     check_world(args)
     if args.gpus > 1 and args.workload in ("dense", "remap", "e2e"):
         raise SystemExit(f"bench.py: workload {args.workload} is single-GPU (--gpus 1)")
+    if args.dump_outputs and args.workload != "pairs":
+        raise SystemExit("bench.py: --dump-outputs is for the pairs workload")
     import torch
     if args.ranks_on_device >= 0 and args.dist_backend != "gloo":
         raise SystemExit("bench.py: --ranks-on-device needs --dist-backend gloo (RCCL refuses "
@@ -729,6 +772,63 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     timed_out = out  # the last timed step's records (torch.cat: a tensor of its own)
+
+    def head(elapsed, value):  # the fields every line of the pairs workload starts with
+        return {
+            "metric": "ERP image-pairs/sec (4k x 4k kpts, 10k RANSAC iters); match-set bit-exact",
+            "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / max(args.steps, 1) * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32+f64",
+            "data": "synthetic (seeded SURF-like descriptors + ERP keypoints, synth.make_pair)",
+            "full": bool(args.full),
+            "config": {"workload": (("configs[1] shape" if args.kpts == 4096 else
+                                     "configs[2] shape" if args.kpts == 2048 else "custom shape") +
+                                    f": {args.kpts}x{args.kpts} kpts/pair, {args.iters} initial_guess "
+                                    f"iters, batch of {args.pairs} independent pairs per step per GPU"),
+                       "kpts": args.kpts, "iters": args.iters, "pairs_per_step_per_gpu": args.pairs,
+                       "streams": S, "matcher": args.matcher,
+                       "parallelism": f"pair-sharded x{world}", "sampler": ("glibc replay (seed 1)" if SAMPLER == 0
+                                   else "Philox4x32-10 + Floyd (seed 1; no reference counterpart)"),
+                       "rccl_world": world if dist is not None and args.dist_backend == "nccl" else None,
+                       "dist_backend": args.dist_backend if dist is not None else None,
+                       "ctx_options": CTX_OPTIONS or None,
+                       "ranks_on_device": args.ranks_on_device if args.ranks_on_device >= 0 else None,
+                       "profile_tag": args.profile_tag,
+                       "inlier_frac": args.inlier_frac, "sigma": args.sigma}}
+
+    def cheap_check(res):  # read off the step's own records (no further GPU work)
+        return {"all_status_ok": bool(np.all(res["status"] == 0)),
+                "mean_abs_euler_err_deg_max": max(
+                    float(np.degrees(np.abs(r["R"] - p["euler_gt"])).mean())
+                    for r, p in zip(res, pairs)),
+                "M_mean": float(res["M"].mean()), "K_mean": float(res["K"].mean()),
+                "consensus_survivors": {"mean": float(res["survivors"].mean()),
+                                        "max": int(res["survivors"].max()),
+                                        "pairs_over_8": np.nonzero(res["survivors"] > 8)[0].tolist()},
+                "near_ties": {"total": int(res["near_ties"].sum()),
+                              "pairs": np.nonzero(res["near_ties"])[0].tolist()}}
+
+    if not args.full:
+        # the plain run ends here: the headline of the timed steps and their records
+        elapsed = t1 - t0
+        if out is None:  # --steps 0: the warm-up's records (one serial pass if there was none)
+            if args.warmup == 0:
+                call_serial()
+            out = torch.cat([sb["res"] for sb in subs])
+        if dist is not None:
+            tt = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            elapsed = float(tt.item())
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, gathered if gathered is not None else out)
+            line = head(elapsed, world * args.pairs * args.steps / elapsed if args.steps > 0 else None)
+            line["check"] = cheap_check(results_to_numpy(out))
+            line["check"]["gathered_records"] = None if gathered is None else int(gathered.shape[0])
+            print(json.dumps(line))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # per-kernel durations: one more step AFTER the timed region, its sub-batches run one after
     # the other with HIP events around every kernel (standalone kernel times; inside the timed
     # region the sub-batches overlap, so events there would also count queueing behind the
@@ -746,6 +846,8 @@ def main():
     elapsed = t1 - t0
     serial_out = torch.cat([sb["res"] for sb in subs])  # the serial pass recomputed the step
     out = timed_out if timed_out is not None else serial_out
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered if gathered is not None else out)
     timed_identical = (None if timed_out is None else
                        bool(torch.equal(timed_out.cpu(), serial_out.cpu())))
     # the same comparison on the result fields only (binned_rows / survivors are work counts):
@@ -777,8 +879,6 @@ def main():
                        "ranks_result_fields_differ": f[1], "pairs_result_fields_differ": f[2],
                        "timed_records_identical": f[0] == 0}
     res = results_to_numpy(out)
-    ok = bool(np.all(res["status"] == 0))
-    err_deg = [float(np.degrees(np.abs(r["R"] - p["euler_gt"])).mean()) for r, p in zip(res, pairs)]
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
@@ -1047,25 +1147,7 @@ def main():
             parity["timed_result_diff_oracle"] = judged
             parity["all_equal"] = False
     line = {
-        "metric": "ERP image-pairs/sec (4k x 4k kpts, 10k RANSAC iters); match-set bit-exact",
-        "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": elapsed / max(args.steps, 1) * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32+f64",
-        "data": "synthetic (seeded SURF-like descriptors + ERP keypoints, synth.make_pair)",
-        "config": {"workload": (("configs[1] shape" if args.kpts == 4096 else
-                                 "configs[2] shape" if args.kpts == 2048 else "custom shape") +
-                                f": {args.kpts}x{args.kpts} kpts/pair, {args.iters} initial_guess "
-                                f"iters, batch of {args.pairs} independent pairs per step per GPU"),
-                   "kpts": args.kpts, "iters": args.iters, "pairs_per_step_per_gpu": args.pairs,
-                   "streams": S, "matcher": args.matcher,
-                   "parallelism": f"pair-sharded x{world}", "sampler": ("glibc replay (seed 1)" if SAMPLER == 0
-                               else "Philox4x32-10 + Floyd (seed 1; no reference counterpart)"),
-                   "rccl_world": world if dist is not None and args.dist_backend == "nccl" else None,
-                   "dist_backend": args.dist_backend if dist is not None else None,
-                   "ctx_options": CTX_OPTIONS or None,
-                   "ranks_on_device": args.ranks_on_device if args.ranks_on_device >= 0 else None,
-                   "profile_tag": args.profile_tag,
-                   "inlier_frac": args.inlier_frac, "sigma": args.sigma},
+        **head(elapsed, value),
         "roofline": roof,
         "roofline_stages": stage_roofs,
         "cpu_baseline": cpu,
@@ -1082,13 +1164,7 @@ def main():
         "exact": (None if parity is None else bool(
             parity["all_equal"] and parity.get("timed_records_identical", True) is not False
             and parity.get("rerun_records_identical", True) is not False)),
-        "check": {"all_status_ok": ok, "mean_abs_euler_err_deg_max": max(err_deg),
-                  "M_mean": float(res["M"].mean()), "K_mean": float(res["K"].mean()),
-                  "consensus_survivors": {"mean": float(res["survivors"].mean()),
-                                          "max": int(res["survivors"].max()),
-                                          "pairs_over_8": np.nonzero(res["survivors"] > 8)[0].tolist()},
-                  "near_ties": {"total": int(res["near_ties"].sum()),
-                                "pairs": np.nonzero(res["near_ties"])[0].tolist()},
+        "check": {**cheap_check(res),
                   "parity": parity,
                   "gathered_records": None if gathered is None else int(gathered.shape[0]),
                   "multi_rank": multi},

@@ -19,6 +19,6 @@ for V in ${VALUES:-0 1}; do
   N=$((N + 1))
   F=gpurun_out/bench_${TAG}_${N}_$(echo "$V" | tr '/' '_')
   if [ -n "${OPT:-}" ]; then PRE=""; ARM="--ctx-option $OPT=$V"; else PRE="$KNOB=$V"; ARM=""; fi
-  echo "== bench ${OPT:-$KNOB}=$V" && env $PRE timeout -k 10 400 python bench.py --no-cpu-baseline --steps ${STEPS:-10} --warmup 2 $ARM ${BENCH_ARGS:-} > $F.json 2> $F.err || { tail -20 $F.err; exit 1; }
+  echo "== bench ${OPT:-$KNOB}=$V" && env $PRE timeout -k 10 400 python bench.py --full --no-cpu-baseline --steps ${STEPS:-10} --warmup 2 $ARM ${BENCH_ARGS:-} > $F.json 2> $F.err || { tail -20 $F.err; exit 1; }
   python scripts/bench_summary.py $F.json 2>/dev/null || python -c "import json;d=json.load(open('$F.json'));print(d['value'], d['ms_per_step'], {k:round(v,2) for k,v in d['stages_ms_serial_step'].items() if v>0.3})"
 done

@@ -6,6 +6,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 bash scripts/gpu_ab.sh || exit 1
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the serial profile step (HIP-event pass) is part of the full run
 for V in ${VALUES:-0 1}; do
   W=$(echo "$V" | tr '/' '_')  # (path-valued knobs: ERP_LIB_PATH variant libraries)
   if [ -n "${OPT:-}" ]; then PRE=""; ARM="--ctx-option $OPT=$V"; else PRE="$KNOB=$V"; ARM=""; fi

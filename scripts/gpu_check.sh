@@ -12,6 +12,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -3 gpurun_out/pytest_gpu_${TAG}.log
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the summary below reads the full line's fields (exact, stage times)
   echo "== bench" && timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench_${TAG}.json \
     2> gpurun_out/bench_${TAG}.err || { tail -20 gpurun_out/bench_${TAG}.err; exit 1; }
   python -c "import json;d=json.load(open('gpurun_out/bench_${TAG}.json'));print(d['value'],d['ms_per_step'],d['exact'],{k:round(v,2) for k,v in d['stages_ms_serial_step'].items() if v>0.1})"

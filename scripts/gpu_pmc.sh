@@ -7,6 +7,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=$1; shift
 i=0
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # every kernel of the full run (profile pass, latency, hard and worst batch)
 for grp in "$@"; do
   timeout -k 10 300 rocprofv3 --pmc $grp -d gpurun_out/pmc_${TAG}_$i -o run --output-format csv -- \
     python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline $BENCH_ARGS > gpurun_out/pmc_${TAG}_$i.log 2>&1 || { tail -5 gpurun_out/pmc_${TAG}_$i.log; exit 1; }

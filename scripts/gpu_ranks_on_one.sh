@@ -5,7 +5,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp; mkdir -p gpurun_out
 TAG=${TAG:-r06b}; N=${N:-2}
-echo "== bench --gpus $N on one device" && timeout -k 10 600 python bench.py --gpus $N --dist-backend gloo \
+echo "== bench --gpus $N on one device" && timeout -k 10 600 python bench.py --full --gpus $N --dist-backend gloo \
   --ranks-on-device 0 --steps 3 --warmup 1 --hard-steps 0 --worst-steps 0 \
   > gpurun_out/bench_ranks${N}_${TAG}.json 2> gpurun_out/bench_ranks${N}_${TAG}.err \
   || { tail -30 gpurun_out/bench_ranks${N}_${TAG}.err; exit 1; }

@@ -26,24 +26,24 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
     || { tail -30 gpurun_out/pytest_gpu_${TAG}.log; exit 1; }
   tail -2 gpurun_out/pytest_gpu_${TAG}.log
 fi
-echo "== bench (default, with cpu baseline)" && timeout -k 10 600 python bench.py --profile-tag ${TAG} \
+echo "== bench (default, with cpu baseline)" && timeout -k 10 600 python bench.py --full --profile-tag ${TAG} \
   > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err || { tail -20 gpurun_out/bench_${TAG}.err; exit 1; }
 tail -c 400 gpurun_out/bench_${TAG}.json
 if [ "${EXTRA_BENCH:-0}" = "1" ]; then
   if [ "${PHILOX:-0}" = "1" ]; then  # (the counter-based sampler: an option, not measured every round)
-    echo "== bench --sampler philox" && timeout -k 10 600 python bench.py --sampler philox --profile-tag ${TAG} \
+    echo "== bench --sampler philox" && timeout -k 10 600 python bench.py --full --sampler philox --profile-tag ${TAG} \
       --hard-steps 0 --worst-steps 0 > gpurun_out/bench_philox_${TAG}.json 2> gpurun_out/bench_philox_${TAG}.err \
       || { tail -20 gpurun_out/bench_philox_${TAG}.err; exit 1; }
     tail -c 300 gpurun_out/bench_philox_${TAG}.json
   fi
   # the worst-case batch as the timed batch, with its own oracle check (a bounded CPU sample of
   # the first pair of every sub-batch, then the second, ...) and timed-vs-serial comparison
-  echo "== bench --main-batch worst" && timeout -k 10 600 python bench.py --main-batch worst --steps 3 \
+  echo "== bench --main-batch worst" && timeout -k 10 600 python bench.py --full --main-batch worst --steps 3 \
     --hard-steps 0 --worst-steps 0 --cpu-seconds 8 --profile-tag ${TAG} > gpurun_out/bench_worst_${TAG}.json \
     2> gpurun_out/bench_worst_${TAG}.err || { tail -20 gpurun_out/bench_worst_${TAG}.err; exit 1; }
   tail -c 300 gpurun_out/bench_worst_${TAG}.json
   echo "== bench configs[2] shape (2048 x 2048 keypoints, 1024 pairs per step)" && timeout -k 10 600 \
-    python bench.py --kpts 2048 --pairs 1024 --hard-steps 0 --worst-steps 0 --profile-tag ${TAG} \
+    python bench.py --full --kpts 2048 --pairs 1024 --hard-steps 0 --worst-steps 0 --profile-tag ${TAG} \
     > gpurun_out/bench_configs2_${TAG}.json 2> gpurun_out/bench_configs2_${TAG}.err \
     || { tail -20 gpurun_out/bench_configs2_${TAG}.err; exit 1; }
   tail -c 300 gpurun_out/bench_configs2_${TAG}.json
@@ -58,13 +58,13 @@ if [ "${EXTRA_BENCH:-0}" = "1" ]; then
 fi
 if [ "${SKIP_PROFILE:-0}" != "1" ]; then
   echo "== rocprofv3 kernel-trace stats" && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${TAG} \
-    -o run --output-format csv -- python3 bench.py --no-cpu-baseline --steps 0 --warmup 2 --profile-tag ${TAG} \
+    -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --steps 0 --warmup 2 --profile-tag ${TAG} \
     > gpurun_out/prof_${TAG}.log 2>&1 || { tail -20 gpurun_out/prof_${TAG}.log; exit 1; }
   echo "== pmc FETCH_SIZE" && timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch_${TAG} -o run \
-    --output-format csv -- python3 bench.py --no-cpu-baseline --steps 0 --warmup 2 --profile-tag ${TAG} \
+    --output-format csv -- python3 bench.py --full --no-cpu-baseline --steps 0 --warmup 2 --profile-tag ${TAG} \
     > gpurun_out/pmc_fetch_${TAG}.log 2>&1 || { tail -20 gpurun_out/pmc_fetch_${TAG}.log; exit 1; }
   echo "== pmc WRITE_SIZE" && timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write_${TAG} -o run \
-    --output-format csv -- python3 bench.py --no-cpu-baseline --steps 0 --warmup 2 --profile-tag ${TAG} \
+    --output-format csv -- python3 bench.py --full --no-cpu-baseline --steps 0 --warmup 2 --profile-tag ${TAG} \
     > gpurun_out/pmc_write_${TAG}.log 2>&1 || { tail -20 gpurun_out/pmc_write_${TAG}.log; exit 1; }
   find gpurun_out/prof_${TAG} gpurun_out/pmc_fetch_${TAG} gpurun_out/pmc_write_${TAG} -name "*.csv"
 fi

@@ -9,6 +9,6 @@ mkdir -p gpurun_out
 for C in ${CONFIGS:-768:4 1024:4}; do
   P=${C%%:*}; S=${C##*:}
   F=gpurun_out/sweep_${P}x${S}
-  echo "== pairs $P streams $S" && timeout -k 10 400 python bench.py --no-cpu-baseline --hard-steps 0 --worst-steps 0 --steps ${STEPS:-8} --warmup 2 --pairs $P --streams $S > $F.json 2> $F.err || { tail -20 $F.err; exit 1; }
+  echo "== pairs $P streams $S" && timeout -k 10 400 python bench.py --full --no-cpu-baseline --hard-steps 0 --worst-steps 0 --steps ${STEPS:-8} --warmup 2 --pairs $P --streams $S > $F.json 2> $F.err || { tail -20 $F.err; exit 1; }
   python -c "import json;d=json.loads(open('$F.json').read().strip().splitlines()[-1]);print(round(d['value']), round(d['ms_per_step'],2), d['overlap'])"
 done
