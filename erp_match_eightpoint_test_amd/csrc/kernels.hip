@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -347,11 +348,12 @@ __device__ __forceinline__ uint32_t mod_small(uint32_t x, uint64_t mt, double r,
 
 // One block of 31 reverse steps i0, i0-1, ..., i0-30 of one lane's replay (ring = the 31-word
 // glibc window, advanced backwards in place).  Returns the block's selection word: bit u set
-// iff step i0-u's index ends in the sample.  bm = the lane's s-bit LDS bitmap, [word][lane],
-// bit SET = position still unresolved (available):
-//   steps i >= s (replay_block_draws):   sel = bm[j];  bm[j] := 0
-//   steps 1 <= i < s (replay_block_prefix): sel = bm[j];  bm[j] := bm[i]
-//   the block straddling s / running below step 1 (replay_block_mixed): per step
+// iff step i0-u's index ends in the sample.  bm = the lane's s-bit LDS bitmap, bit SET =
+// position still unresolved (available) -- lane-major, [word][lane], in the latency kernels and
+// the split replay (described here), position-major in the throughput kernel (further down):
+//   steps i >= s (replay_block_draws*):   sel = bm[j];  bm[j] := 0
+//   steps 1 <= i < s (replay_block_prefix*): sel = bm[j];  bm[j] := bm[i]
+//   the block straddling s / running below step 1 (replay_block_mixed*): per step
 // A position j >= s is clamped to s (ERP_SAMPLER_CLAMP, default since r05): bit s is 0 (the
 // prologue clears every word of the allocation past the positions < s) and its word is
 // allocated, so no LDS access leaves the workgroup's allocation.  Until r05 the clamp was left
@@ -403,12 +405,62 @@ __device__ __forceinline__ void lds_wait_step(uint32_t& o, int v) {
 #ifndef ERP_SAMPLER_CLAMP
 #define ERP_SAMPLER_CLAMP 1
 #endif
+
+// ---- throughput blocks (sampler_kernel<0>): the bitmap position-major ----------------------
+// The throughput kernel turns the bitmap round: one word per POSITION, one bit per LANE, words
+// [half][position] (half = lane >> 5, bit lane & 31; P position words per half).  A lane's bit
+// mask and bit index are then constants held in registers and a position's address is one
+// v_lshl_add_u32 of j -- the lane-major form builds word index, bit mask and bit index from j at
+// every draw.  Per draw step: clamp, address, ds_and_rtn_b32(~lanebit), v_bfe_u32 of the old word
+// at the lane's bit, placement (9 VALU with the generator and the modulo, against 11).  A half's
+// 32 lanes address random words, i.e. random LDS banks: the conflicts are hidden at 4 waves per
+// SIMD (scripts/dev/sampler_sol.hip V8 / V9 measured it: sampler 6.68 -> 6.05 ms per 768-pair
+// step, profiles/r07a_ab_sampler_posmajor.txt), not where a wave is alone on its SIMD, so the
+// latency kernels below keep the lane-major bitmap.  ([position][half] would put a half's lanes
+// on the 16 even banks only.)
+// The clamp: most draws have j >= s (i runs from M - 1 down to s = M / 4).  Clamped to the one
+// word s they would make every wave-op a 32-lane same-address returning atomic per half, which
+// the LDS serialises (the probe's V5 / V6: 4.5x slower).  Every word from s upwards is clear, so
+// lane l clamps to position s + (l & 31) instead: the clamped lanes sit on 32 consecutive
+// words, i.e. distinct banks (32 more position words allocated per half, all clear; still one
+// v_min_u32).  Polarity and the selection words are the lane-major kernels', bit for bit.
+struct PmLane {
+    uint32_t base;  // LDS byte address of the half's position 0
+    uint32_t bit;   // 1 << (lane & 31)
+    uint32_t nbit;  // ~bit
+    uint32_t idx;   // lane & 31
+    uint32_t cap;   // s + idx: the lane's clamp word for the draws (positions >= s are all clear)
+};
+__device__ __forceinline__ uint32_t lds_and_rtn(uint32_t addr, uint32_t data) {
+    uint32_t old;
+    asm volatile("ds_and_rtn_b32 %0, %1, %2" : "=v"(old) : "v"(addr), "v"(data) : "memory");
+    return old;
+}
+__device__ __forceinline__ uint32_t pm_addr(uint32_t base, uint32_t j) {
+    uint32_t a;
+    asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(a) : "v"(j), "v"(base));
+    return a;
+}
+// ds_read_b32 at a constant byte offset (no address arithmetic per step)
+template <int OFF>
+__device__ __forceinline__ uint32_t lds_read_off(uint32_t a, bool clobber) {
+    uint32_t rd;
+    if (clobber) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(rd) : "v"(a), "n"(OFF) : "memory");
+    else asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(rd) : "v"(a), "n"(OFF));
+    return rd;
+}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a
+// constant expression in the body (the reads' immediate offsets)
+template <typename F, int... U>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, U...>, F&& f) {
+    (f(std::integral_constant<int, U>{}), ...);
+}
+
 // steps i >= s: one LDS op per draw, positions clamped to s, no validity select
-template <bool I24, int RS = 8>
-__device__ __forceinline__ uint32_t replay_block_draws(uint32_t (&ring)[31], uint32_t* bm,
-                                                       int lane, int i0, int s,
+template <bool I24>
+__device__ __forceinline__ uint32_t replay_block_draws(uint32_t (&ring)[31], const PmLane& pl,
+                                                       int i0, int s,
                                                        const double* __restrict__ rtab) {
-    const uint32_t bm_lane = (uint32_t)(size_t)(lds_u32*)bm + 4u * (uint32_t)lane;
     double rt[31];  // 1/(i+1) of the block's steps: scalar loads (uniform index)
     StepDiv mt[31];  // (I24: the d >= 256 divisor constants)
 #pragma unroll
@@ -416,8 +468,7 @@ __device__ __forceinline__ uint32_t replay_block_draws(uint32_t (&ring)[31], uin
         if (I24 || ERP_SAMPLER_MAGIC) mt[u] = step_div(rtab, i0 - u + 1);
         else rt[u] = rtab[i0 - u + 1];
     }
-    const uint32_t zero = 0;
-    uint32_t olds[31], pos[31];
+    uint32_t olds[31];
     uint32_t nw = 0;
 #pragma unroll
     for (int u = 0; u < 31 + kReplayLag; u++) {
@@ -428,84 +479,37 @@ __device__ __forceinline__ uint32_t replay_block_draws(uint32_t (&ring)[31], uin
             ring[slot] = rv - ring[(slot + 28) % 31];
             uint32_t j = I24 ? mod_i24(rv >> 1, mt[u], ii + 1)
                              : mod_small(rv >> 1, (uint64_t)mt[u], ERP_SAMPLER_MAGIC ? 0.0 : rt[u], ii + 1);
-            if (ERP_SAMPLER_CLAMP) j = min(j, (uint32_t)s);  // (bit s: clear and allocated)
-            olds[u] = lds_mskor_rtn(lds_word_addr<RS>(bm_lane, j), 1u << (j & 31), zero);
-            pos[u] = j;
+            if (ERP_SAMPLER_CLAMP) j = min(j, pl.cap);  // (words s .. s + 31: clear and allocated)
+            olds[u] = lds_and_rtn(pm_addr(pl.base, j), pl.nbit);
         }
         const int v = u - kReplayLag;
         if (v >= 0) {
             lds_wait_step(olds[v], v);
-            nw |= __builtin_amdgcn_ubfe(olds[v], pos[v], 1) << v;
+            nw |= __builtin_amdgcn_ubfe(olds[v], pl.idx, 1) << v;
         }
     }
     return nw;
 }
 
-// steps 1 <= i < s with the block's own 31 bits bm[i0-30 .. i0] in one register: bm[i] is a
-// constant-position bit extract, the bit copy bm[j] := bm[i] is one masked OR (returning old
-// bm[j]), and a step that writes inside the window updates it with one bfi (out-of-window j
-// lands on the unused bit 31).  ~17 VALU + 1 DS per step.
-template <bool I24, int RS = 8>
-__device__ __forceinline__ uint32_t replay_block_prefix(uint32_t (&ring)[31], uint32_t* bm,
-                                                        int lane, int i0,
-                                                        const double* __restrict__ rtab) {
-    const uint32_t bm_lane = (uint32_t)(size_t)(lds_u32*)bm + 4u * (uint32_t)lane;
-    double rt[31];
-#pragma unroll
-    for (int u = 0; u < 31; u++) rt[u] = rtab[i0 - u + 1];
-    const int base = i0 - 30;  // >= 1
-    const int wA = i0 >> 5, wB = base >> 5;
-    const uint32_t hi = bm[bm_index<RS>(wA, lane)], lo = bm[bm_index<RS>(wB, lane)];
-    uint32_t win = wA == wB ? (lo >> (base & 31)) : __builtin_amdgcn_alignbit(hi, lo, base & 31);
-    uint32_t olds[31], pos[31];
-    uint32_t nw = 0;
-#pragma unroll
-    for (int u = 0; u < 31 + kReplayLag; u++) {
-        if (u < 31) {
-            const int ii = i0 - u;
-            const int slot = 30 - u;
-            const uint32_t rv = ring[slot];
-            ring[slot] = rv - ring[(slot + 28) % 31];
-            const uint32_t j = I24 ? mod_rup_i24(rv >> 1, rt[u], ii + 1)
-                                   : mod_rup(rv >> 1, rt[u], (double)(ii + 1));
-            const uint32_t bsp = (uint32_t)__builtin_amdgcn_sbfe((int)win, 30 - u, 1);  // bm[i]
-            const uint32_t bit = 1u << (j & 31);
-            olds[u] = lds_mskor_rtn(lds_word_addr<RS>(bm_lane, j), bit, bsp & bit);
-            pos[u] = j;
-            const uint32_t t = min(j - (uint32_t)base, 31u);
-            const uint32_t m = 1u << t;
-            win = (win & ~m) | (bsp & m);
-        }
-        const int v = u - kReplayLag;
-        if (v >= 0) {
-            lds_wait_step(olds[v], v);
-            nw |= __builtin_amdgcn_ubfe(olds[v], pos[v], 1) << v;
-        }
-    }
-    return nw;
-}
-
-// The same steps with bm[i] read back from LDS per step instead of a register window (no
-// window bookkeeping: ~13.5 instead of ~16.5 VALU per step).  A wave's LDS ops complete in
-// order, so the read of bm[i] issued after the previous step's masked OR sees it; the read is
+// steps 1 <= i < s: bm[i] is read back from LDS per step -- one word at a wave-uniform address
+// per half, a broadcast -- the copied bit is rd & lanebit and the bit copy bm[j] := bm[i] one
+// masked OR returning the old bm[j] (~10 VALU per step; j <= i < s: no clamp).  A wave's LDS ops
+// complete in order, so the read issued after the previous step's masked OR sees it; it is
 // issued before the step's modulo, whose VALU work (and the other waves') covers its latency.
-#ifndef ERP_PREFIX_READ
-#define ERP_PREFIX_READ 1
-#endif
-template <bool I24, int RS = 8>
-__device__ __forceinline__ uint32_t replay_block_prefix_rd(uint32_t (&ring)[31], uint32_t* bm,
-                                                           int lane, int i0,
+template <bool I24>
+__device__ __forceinline__ uint32_t replay_block_prefix_rd(uint32_t (&ring)[31], const PmLane& pl,
+                                                           int i0,
                                                            const double* __restrict__ rtab) {
-    const uint32_t bm_lane = (uint32_t)(size_t)(lds_u32*)bm + 4u * (uint32_t)lane;
     // the reads are volatile asm, ordered against the masked ORs as volatile asm; only the
     // first carries a memory clobber (every earlier bitmap access is emitted before it, and the
     // block's reciprocal loads above it, where they merge into wide scalar loads -- sunk into
     // the steps one by one, their 31 addresses spill)
     double rt[31];
     StepDiv mt[31];
-    uint32_t nw = 0, prev = 0, ppos = 0;
-#pragma unroll
-    for (int u = 0; u < 31; u++) {
+    uint32_t nw = 0, prev = 0;
+    const uint32_t rbase = pl.base + 4u * (uint32_t)(i0 - 30);  // the word of step i0 - 30 (>= 1)
+    static_for(std::make_integer_sequence<int, 31>{}, [&](auto uc) __attribute__((always_inline)) {
+        constexpr int u = decltype(uc)::value;
         const int ii = i0 - u;  // uniform, >= 1
         if (u == 0 || u == 16)  // the reciprocals in two halves (SGPR pressure)
 #pragma unroll
@@ -513,28 +517,51 @@ __device__ __forceinline__ uint32_t replay_block_prefix_rd(uint32_t (&ring)[31],
                 if (I24 || ERP_SAMPLER_MAGIC) mt[k] = step_div(rtab, i0 - k + 1);
                 else rt[k] = rtab[i0 - k + 1];
             }
-        uint32_t rd;
-        const uint32_t ra = bm_lane + ((uint32_t)(ii >> 5) << RS);
-        if (u == 0 || u == 16)  // the memory clobber holds the half's loads (merged) above it
-            asm volatile("ds_read_b32 %0, %1" : "=v"(rd) : "v"(ra) : "memory");
-        else
-            asm volatile("ds_read_b32 %0, %1" : "=v"(rd) : "v"(ra));
+        // bm[i] (the memory clobber holds the half's loads (merged) above it)
+        uint32_t rd = lds_read_off<4 * (30 - u)>(rbase, u == 0 || u == 16);
         const int slot = 30 - u;
         const uint32_t rv = ring[slot];
         ring[slot] = rv - ring[(slot + 28) % 31];
         const uint32_t j = I24 ? mod_i24(rv >> 1, mt[u], ii + 1)
                                : mod_small(rv >> 1, (uint64_t)mt[u], ERP_SAMPLER_MAGIC ? 0.0 : rt[u], ii + 1);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rd), "+v"(prev));
-        if (u > 0) nw |= __builtin_amdgcn_ubfe(prev, ppos, 1) << (u - 1);
-        const uint32_t bsp = (uint32_t)__builtin_amdgcn_sbfe((int)rd, ii & 31, 1);  // bm[i]
-        const uint32_t bit = 1u << (j & 31);
-        prev = lds_mskor_rtn(lds_word_addr<RS>(bm_lane, j), bit, bsp & bit);
-        ppos = j;
-    }
+        if constexpr (u > 0) nw |= __builtin_amdgcn_ubfe(prev, pl.idx, 1) << (u - 1);
+        prev = lds_mskor_rtn(pm_addr(pl.base, j), pl.bit, rd & pl.bit);
+    });
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(prev) : : "memory");
-    return nw | (__builtin_amdgcn_ubfe(prev, ppos, 1) << 30);
+    return nw | (__builtin_amdgcn_ubfe(prev, pl.idx, 1) << 30);
 }
 
+// the block that straddles s, and the last block that runs below step 1, on the position-major
+// bitmap: at most two per iteration, so each step is done on its own (compiler-tracked atomics;
+// bmh = the half's position 0).  Steps below 1 do nothing.
+__device__ __forceinline__ uint32_t replay_block_mixed_pm(uint32_t (&ring)[31], uint32_t* bmh,
+                                                          const PmLane& pl, int i0, int s,
+                                                          const double* __restrict__ rtab) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int u = 0; u < 31; u++) {
+        const int ii = i0 - u;  // uniform
+        const int slot = 30 - u;
+        const uint32_t rv = ring[slot];
+        ring[slot] = rv - ring[(slot + 28) % 31];
+        if (ii < 1) continue;
+#if ERP_SAMPLER_MAGIC
+        uint32_t j = mod_small(rv >> 1, (uint64_t)step_div(rtab, ii + 1), 0.0, ii + 1);
+#else
+        uint32_t j = mod_rup(rv >> 1, rtab[ii + 1], (double)(ii + 1));
+#endif
+        j = min(j, (uint32_t)s);  // (always: the compiler-tracked accesses stay in the allocation)
+        // bm[i] (read before the clear: j = i keeps the bit)
+        const uint32_t bi = ii < s ? bmh[ii] & pl.bit : 0u;
+        const uint32_t old = atomicAnd(&bmh[j], pl.nbit);
+        if (ii < s) atomicOr(&bmh[j], bi);
+        word |= __builtin_amdgcn_ubfe(old, pl.idx, 1) << u;
+    }
+    return word;
+}
+
+// ---- lane-major blocks (the latency kernels and the split replay) -------------------------
 // the block that straddles s, and the last block that runs below step 1: at most two per
 // iteration, so each step is done on its own (compiler-tracked atomics; keeps the kernel's
 // register budget at the other blocks' level).  Steps below 1 do nothing.
@@ -732,31 +759,29 @@ __device__ __forceinline__ uint32_t replay_block_lat(uint32_t (&ring)[31], uint3
 }
 
 // the 31 reverse steps i .. i-30 of one lane's replay, by block kind (uniform: i and s are)
-template <int RS>
-__device__ __forceinline__ uint32_t replay_block(uint32_t (&ring)[31], uint32_t* bm, int lane,
-                                                 int i, int s, const double* __restrict__ rtab) {
-    if (i - 30 >= s && i - 30 >= 255) return replay_block_draws<true, RS>(ring, bm, lane, i, s, rtab);
-    if (i - 30 >= s) return replay_block_draws<false, RS>(ring, bm, lane, i, s, rtab);
-    if (i < s && i - 30 >= 255)
-        return ERP_PREFIX_READ ? replay_block_prefix_rd<true, RS>(ring, bm, lane, i, rtab)
-                               : replay_block_prefix<true, RS>(ring, bm, lane, i, rtab);
-    if (i < s && i - 30 >= 1)
-        return ERP_PREFIX_READ ? replay_block_prefix_rd<false, RS>(ring, bm, lane, i, rtab)
-                               : replay_block_prefix<false, RS>(ring, bm, lane, i, rtab);
-    return replay_block_mixed<RS>(ring, bm, lane, i, s, rtab);
+__device__ __forceinline__ uint32_t replay_block(uint32_t (&ring)[31], uint32_t* bmh,
+                                                 const PmLane& pl, int i, int s,
+                                                 const double* __restrict__ rtab) {
+    if (i - 30 >= s && i - 30 >= 255) return replay_block_draws<true>(ring, pl, i, s, rtab);
+    if (i - 30 >= s) return replay_block_draws<false>(ring, pl, i, s, rtab);
+    if (i < s && i - 30 >= 255) return replay_block_prefix_rd<true>(ring, pl, i, rtab);
+    if (i < s && i - 30 >= 1) return replay_block_prefix_rd<false>(ring, pl, i, rtab);
+    return replay_block_mixed_pm(ring, bmh, pl, i, s, rtab);
 }
 
 // One lane = one iteration; writes the iteration's selection bitmap in block space:
 // sel[p][w][b][lane] bit u <-> index i = M-1-31b-u (b = 0 .. (M-1)/31), exactly s bits set.
-// MODE 0: the throughput blocks; 2 / 3: the latency blocks, step by step / positions first
-// (constants prefetched one block ahead by vector loads, two blocks per loop trip so that the two
-// constant sets alternate without register copies)
+// MODE 0: the throughput blocks on the position-major bitmap (nalloc = position words per half,
+// the allocation 2 * nalloc words); 2 / 3: the latency blocks, step by step / positions first,
+// on the lane-major bitmap (nalloc words per lane; constants prefetched one block ahead by vector
+// loads, two blocks per loop trip so that the two constant sets alternate without register
+// copies)
 template <int MODE>
 __global__ __launch_bounds__(64) void sampler_kernel(
     const int32_t* __restrict__ counts, const uint32_t* __restrict__ wins, int nwaves, int nbw,
     double sample_frac, const double* __restrict__ rtab, uint32_t* __restrict__ selw,
     int32_t* __restrict__ flags, int nalloc) {
-    extern __shared__ uint32_t bm[];  // [nwords][64]
+    extern __shared__ uint32_t bm[];  // MODE 0: [2][nalloc]; else [nalloc][64]
     const int p = blockIdx.y, w = blockIdx.x, lane = wave_lane();
     const int M = counts[p];
     const int s = (int)(M * sample_frac);
@@ -768,8 +793,22 @@ __global__ __launch_bounds__(64) void sampler_kernel(
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 3\n\ts_nop 3" ::: "memory");
     // positions < s available, every other bitmap word of the allocation (nalloc words: the
     // batch's largest s, rounded up to the allocation granule) clear
-    for (int k = 0; k < nalloc; k++)
-        bm[k * 64 + lane] = k < (s >> 5) ? ~0u : k == (s >> 5) ? (1u << (s & 31)) - 1u : 0u;
+    if (MODE == 0) {
+        // (position words < s all ones for both halves; every lane's later accesses read words
+        // other lanes wrote: the workgroup is one wave, whose LDS ops complete in order)
+        for (int k = lane; k < nalloc; k += 64) bm[k] = bm[nalloc + k] = k < s ? ~0u : 0u;
+        __syncthreads();
+    } else {
+        for (int k = 0; k < nalloc; k++)
+            bm[k * 64 + lane] = k < (s >> 5) ? ~0u : k == (s >> 5) ? (1u << (s & 31)) - 1u : 0u;
+    }
+    uint32_t* bmh = bm + (lane >> 5) * nalloc;  // (MODE 0) the half's position 0
+    PmLane pl;
+    pl.base = (uint32_t)(size_t)(lds_u32*)bmh;
+    pl.bit = 1u << (lane & 31);
+    pl.nbit = ~pl.bit;
+    pl.idx = (uint32_t)(lane & 31);
+    pl.cap = (uint32_t)s + pl.idx;
     uint32_t ring[31];
     {
         const uint32_t* wi = wins + ((size_t)p * nwaves + w) * 31 * 64 + lane;
@@ -803,9 +842,10 @@ __global__ __launch_bounds__(64) void sampler_kernel(
             emit(replay_block_lat<MODE == 3, 8>(ring, bm, lane, i, s, kb, rtab, cb));
         }
     } else {
-        while (i >= 1) emit(replay_block<8>(ring, bm, lane, i, s, rtab));
+        while (i >= 1) emit(replay_block(ring, bmh, pl, i, s, rtab));
     }
-    if (bm[lane] & 1u) {  // position 0 still unresolved: its value 0 stays in the prefix
+    // position 0 still unresolved: its value 0 stays in the prefix
+    if (MODE == 0 ? (bmh[0] & pl.bit) != 0u : (bm[lane] & 1u) != 0u) {
         lastw |= 1u << u0;
         emitted++;
     }
@@ -4670,8 +4710,10 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
         ERP_LAUNCH(sampler_window_kernel, dim3(nwaves, sh.n_pairs), dim3(64), 0, st, counts,
                            polyR, polyQ, w0, nwaves, sample_frac, wins);
     } else {
-        // positions 0 .. max_s, rounded up to the LDS allocation granule (1280 B = 5 words on
-        // gfx950, scripts/dev/lds_oob.hip) so that no word of the allocation goes uncleared
+        // the lane-major bitmap (latency kernels, split replay): positions 0 .. max_s, rounded up
+        // to the LDS allocation granule (1280 B = 5 words per lane on gfx950,
+        // scripts/dev/lds_oob.hip) so that no word of the allocation goes uncleared
+        // (s up to 16 383 at the 65 535-keypoint cap: 515 words x 256 B = 129 KB)
         const int nwords = (sh.max_s / 32 + 1 + 4) / 5 * 5;
         const size_t shmem = (size_t)nwords * 64 * sizeof(uint32_t);
         // The latency blocks (modes 2 / 3) where the launch leaves most SIMDs with at most one
@@ -4680,14 +4722,17 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
         const int lat = sh.sampler_lat >= 0 ? sh.sampler_lat
                                             : (long)nwaves * sh.n_pairs <= 1024 ? kSamplerLatMode : 0;
         const int mode = lat == 1 ? 2 : lat == 2 ? 3 : 0;
-        // (s up to 16 383 at the 65 535-keypoint cap: 515 words x 256 B = 129 KB)
+        // the throughput kernel's position-major bitmap: positions 0 .. max_s + 31 (the lanes'
+        // clamp words) for each half-wave, the two halves together rounded up to the granule
+        // (320 words) -- the lane-major size within a granule (s up to 16 383: 2 x 16 480 words
+        // = 129 KB)
+        const int npos = (2 * (sh.max_s + 32) + 319) / 320 * 160;
+        const size_t shmem_pm = (size_t)npos * 2 * sizeof(uint32_t);
         const void* fns[4] = {(const void*)sampler_kernel<0>, nullptr,
                               (const void*)sampler_kernel<2>, (const void*)sampler_kernel<3>};
-        const hipError_t le = ensure_dyn_lds(fns[mode], shmem);
-        if (le != hipSuccess) return le;
-#define ERP_SAMPLER_LAUNCH(M)                                                                  \
-    ERP_LAUNCH(sampler_kernel<M>, dim3(nwaves, sh.n_pairs), dim3(64), shmem, st, counts, wins, \
-               nwaves, sh.sel_words, sample_frac, rtab, selw, flags, nwords)
+#define ERP_SAMPLER_LAUNCH(M, LDS, NALLOC)                                                     \
+    ERP_LAUNCH(sampler_kernel<M>, dim3(nwaves, sh.n_pairs), dim3(64), LDS, st, counts, wins,   \
+               nwaves, sh.sel_words, sample_frac, rtab, selw, flags, NALLOC)
         // the split replay (sampler_split_kernel) where the launch has <= 256 workgroups of
         // 64 iterations (one pair at <= 16k iterations) and its 7 bitmaps fit the CU's LDS;
         // sh.sampler_split (ERP_OPT_SAMPLER_SPLIT) = 0 / 1 forces it off / on (when the LDS fits)
@@ -4702,10 +4747,12 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
                        flags, nwords);
             return hipGetLastError();
         }
+        const hipError_t le = ensure_dyn_lds(fns[mode], mode == 0 ? shmem_pm : shmem);
+        if (le != hipSuccess) return le;
         switch (mode) {
-            case 2: ERP_SAMPLER_LAUNCH(2); break;
-            case 3: ERP_SAMPLER_LAUNCH(3); break;
-            default: ERP_SAMPLER_LAUNCH(0); break;
+            case 2: ERP_SAMPLER_LAUNCH(2, shmem, nwords); break;
+            case 3: ERP_SAMPLER_LAUNCH(3, shmem, nwords); break;
+            default: ERP_SAMPLER_LAUNCH(0, shmem_pm, npos); break;
         }
 #undef ERP_SAMPLER_LAUNCH
     }
