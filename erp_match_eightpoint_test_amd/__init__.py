@@ -9,7 +9,9 @@ Host-side mirror of the reference's hot-path classes (Kitsunetic/ERP_match_eight
 * ``epipolar_tool`` / ``feature_matcher.draw_match`` -- the visual outputs
   (src/epipolar_tool.cpp:7-128, src/feature_matcher.cpp:61-86)
 * ``PairBatchRunner`` -- the batched hot path: match -> gather -> find for many ERP pairs,
-  i.e. what src/automatic.cpp:117-126 runs per pair, as one sequence of gfx950 kernels.
+  i.e. what src/automatic.cpp:117-126 runs per pair, as one sequence of gfx950 kernels
+  (``run`` from descriptors, ``run_images`` from the ERP images via
+  ``spherical_surf.do_all_batch``).
 
 Every call goes through the C ABI of ``lib/liberp_match.so`` (include/erp_match.h); there is
 no CPU fallback.  Arrays are numpy (host, synchronous) or torch CUDA tensors (device,
@@ -437,6 +439,87 @@ class spherical_surf:  # noqa: N801  (reference class name)
                     fm.draw_match(im_left, im_right, kl, kr))
         return kl, kr, int(m.shape[0]), int(keys[0].shape[0])
 
+    def pack_band_features(self, kp, desc, counts, W: int, H: int):
+        """erp_pack_band_features_dev: SURF's padded output for the bands of P pairs in the
+        order [pair][left, right][n0..n3] -- kp uint8 [8P, max_kp, 28], desc float32
+        [8P, max_kp, 64] (feature_matcher.surf_dev's layout), counts int32 [8P] (CUDA tensor or
+        host array; max_nq / max_nt come from a host copy) -- of W x H ERP images -> the dict
+        do_all_batch returns."""
+        import torch
+        if not (isinstance(kp, torch.Tensor) and isinstance(desc, torch.Tensor) and kp.is_cuda
+                and desc.is_cuda and kp.dtype == torch.uint8 and desc.dtype == torch.float32
+                and kp.is_contiguous() and desc.is_contiguous() and kp.dim() == 3
+                and desc.dim() == 3 and kp.shape[2] == 28 and desc.shape[2] == 64
+                and kp.shape[:2] == desc.shape[:2] and kp.shape[0] % 8 == 0
+                and kp.shape[1] >= 1):
+            raise ValueError("kp / desc are contiguous CUDA tensors uint8 [8P, max_kp, 28] / "
+                             "float32 [8P, max_kp, 64]")
+        n8, max_kp = kp.shape[:2]
+        if isinstance(counts, torch.Tensor):
+            host = counts.detach().cpu().numpy()
+        else:
+            host = np.asarray(counts)
+        host = np.ascontiguousarray(host, np.int32).reshape(-1)
+        if host.shape[0] != n8:
+            raise ValueError("counts must have one entry per band image")
+        if W < 1 or H < 4:
+            raise ValueError("pack_band_features needs W >= 1 and H >= 4")
+        cnt = torch.from_numpy(host).to(kp.device)
+        c = np.clip(host, 0, max_kp).reshape(-1, 2, 4).astype(np.int64)
+        per = c.sum(axis=2)                                      # [P, 2]
+        rows_l, rows_r = int(per[:, 0].sum()), int(per[:, 1].sum())
+        buf = _PackedBuffers(n8 // 8, rows_l, rows_r, kp.device)
+        pk = buf.struct()
+        check(self.L.erp_pack_band_features_dev(self.ctx.h, kp.data_ptr(), desc.data_ptr(),
+                                                cnt.data_ptr(), n8 // 8, max_kp, W, H,
+                                                C.byref(pk),
+                                                torch.cuda.current_stream(kp.device).cuda_stream),
+              "erp_pack_band_features_dev")
+        out = buf.result(rows_l, rows_r)
+        out["max_nq"] = int(per[:, 0].max()) if len(per) else 0
+        out["max_nt"] = int(per[:, 1].max()) if len(per) else 0
+        return out
+
+    def do_all_batch(self, lefts, rights, max_kp: int = 16384, fill: int = 0,
+                     max_group_pairs: int = 0, **surf_params):
+        """do_all up to the match for P pairs at once, on the device: CUDA uint8 [P, H, W, 3]
+        left / right ERP batches -> bands -> SURF -> un-rotation + concatenation, as the dict
+        of PairBatchRunner.run's arguments (desc_l, desc_r, kp_l, kp_r, off_l, off_r, width,
+        height, max_nq, max_nt) plus band_counts [P, 2, 4].  Output buffers and max_kp grow and
+        the call repeats while it reports an overflow (erp_image_pairs_features_dev);
+        ``last_info`` keeps the final call's erp_image_batch_info."""
+        return self._image_pairs(lefts, rights, max_kp, fill, max_group_pairs, surf_params,
+                                 lambda *a: self.L.erp_image_pairs_features_dev(*a),
+                                 "erp_image_pairs_features_dev")
+
+    def _image_pairs(self, lefts, rights, max_kp, fill, max_group_pairs, surf_params, launch,
+                     where):
+        """the grow-and-retry loop around a library call with erp_image_pairs_features_dev's
+        leading arguments (ctx .. info, stream)"""
+        import torch
+        lefts, rights = _image_batch_dev(lefts, rights)
+        if lefts.device.index != self.ctx.device:
+            raise ValueError(f"images must be on the context's device cuda:{self.ctx.device}")
+        n_pairs, H, W = lefts.shape[:3]
+        prm = _surf_params(self.L, surf_params)
+        st = torch.cuda.current_stream(lefts.device).cuda_stream
+        cap_l = cap_r = 1024 * max(n_pairs, 1)
+        while True:
+            buf = _PackedBuffers(n_pairs, cap_l, cap_r, lefts.device)
+            pk = buf.struct()
+            info = capi.ImageBatchInfo()
+            check(launch(self.ctx.h, lefts.data_ptr(), rights.data_ptr(), n_pairs, W, H,
+                         C.byref(prm), max_kp, fill, max_group_pairs, C.byref(pk), C.byref(info),
+                         st), where)
+            if info.fits:
+                break
+            max_kp = max(max_kp, info.need_kp)
+            cap_l, cap_r = max(cap_l, info.rows_l), max(cap_r, info.rows_r)
+        self.last_info = {f: getattr(info, f) for f, _ in capi.ImageBatchInfo._fields_}
+        out = buf.result(info.rows_l, info.rows_r)
+        out["max_nq"], out["max_nt"] = info.max_nq, info.max_nt
+        return out
+
     def unrotate_band_keypoints(self, key, counts, width: int, height: int):
         """do_all's keypoint step (src/spherical_surf.cpp:120-144), in place on the band
         keypoints concatenated n0, n1, n2, n3 (CUDA float32 [n, 2]); counts = 4 band sizes"""
@@ -449,6 +532,62 @@ class spherical_surf:  # noqa: N801  (reference class name)
                                                      torch.cuda.current_stream().cuda_stream),
               "unrotate_band_keypoints")
         return key
+
+
+def _image_batch_dev(lefts, rights):
+    """the [P, H, W, 3] image batches of do_all_batch / run_images, checked before any call"""
+    import torch
+    for t in (lefts, rights):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8
+                and t.dim() == 4 and t.shape[3] == 3 and t.is_contiguous()):
+            raise ValueError("image batches are contiguous CUDA uint8 tensors [P, H, W, 3]")
+    if lefts.shape != rights.shape or lefts.device != rights.device:
+        raise ValueError("lefts and rights differ in shape or device")
+    if lefts.shape[1] < 4 or lefts.shape[2] < 1:
+        raise ValueError("images need H >= 4 and W >= 1")
+    return lefts, rights
+
+
+def _surf_params(L, params):
+    prm = capi.SurfParams()
+    L.erp_surf_params_default(C.byref(prm))
+    for k, v in params.items():
+        if k not in dict(capi.SurfParams._fields_):
+            raise ValueError(f"unknown SURF parameter {k!r}")
+        setattr(prm, k, v)
+    return prm
+
+
+class _PackedBuffers:
+    """caller-owned outputs of the pack step (erp_packed_pairs) as torch tensors"""
+
+    def __init__(self, n_pairs: int, cap_l: int, cap_r: int, device):
+        import torch
+        f32, i64, i32 = torch.float32, torch.int64, torch.int32
+        self.cap = (cap_l, cap_r)
+        self.t = {"desc_l": torch.empty((max(cap_l, 1), 64), dtype=f32, device=device),
+                  "desc_r": torch.empty((max(cap_r, 1), 64), dtype=f32, device=device),
+                  "kp_l": torch.empty((max(cap_l, 1), 2), dtype=f32, device=device),
+                  "kp_r": torch.empty((max(cap_r, 1), 2), dtype=f32, device=device),
+                  "off_l": torch.zeros(n_pairs + 1, dtype=i64, device=device),
+                  "off_r": torch.zeros(n_pairs + 1, dtype=i64, device=device),
+                  "width": torch.zeros(max(n_pairs, 1), dtype=i32, device=device),
+                  "height": torch.zeros(max(n_pairs, 1), dtype=i32, device=device),
+                  "band_counts": torch.zeros((max(n_pairs, 1), 2, 4), dtype=i32, device=device)}
+        self.n_pairs = n_pairs
+
+    def struct(self) -> "capi.PackedPairs":
+        t = self.t
+        return capi.PackedPairs(*[t[k].data_ptr() for k in
+                                  ("desc_l", "desc_r", "kp_l", "kp_r", "off_l", "off_r", "width",
+                                   "height", "band_counts")], self.cap[0], self.cap[1])
+
+    def result(self, rows_l: int, rows_r: int) -> dict:
+        t, n = self.t, self.n_pairs
+        return {"desc_l": t["desc_l"][:rows_l], "desc_r": t["desc_r"][:rows_r],
+                "kp_l": t["kp_l"][:rows_l], "kp_r": t["kp_r"][:rows_r], "off_l": t["off_l"],
+                "off_r": t["off_r"], "width": t["width"][:n], "height": t["height"][:n],
+                "band_counts": t["band_counts"][:n]}
 
 
 class PairBatchRunner:
@@ -510,6 +649,37 @@ class PairBatchRunner:
         if self.reuse_outputs:
             self._outs[key] = outs
         return self._launch(b, ratio, outs, stream, dev)
+
+    def run_images(self, lefts, rights, ratio: float = 0.3, want=(), max_kp: int = 16384,
+                   fill: int = 0, max_group_pairs: int = 0, **surf_params):
+        """run() from the ERP images: CUDA uint8 [P, H, W, 3] left / right batches ->
+        spherical_surf.do_all_batch's packed batch -> match -> gather -> find -> the same
+        ``outs`` dict as run().  Without optional outputs this is one library call
+        (erp_image_pairs_run); with them (their shapes depend on the packed batch's max_nq) it
+        is do_all_batch followed by run().  ``last_packed`` keeps the packed batch.  Not
+        graph-capturable (the feature stage synchronises per group of pairs)."""
+        import torch
+        lefts, rights = _image_batch_dev(lefts, rights)
+        n_pairs = lefts.shape[0]
+        ss = spherical_surf(ctx=self.ctx)
+        if want and n_pairs:
+            p = ss.do_all_batch(lefts, rights, max_kp=max_kp, fill=fill,
+                                max_group_pairs=max_group_pairs, **surf_params)
+            self.last_packed, self.last_info = p, ss.last_info
+            return self.run(*[p[k] for k in ("desc_l", "desc_r", "kp_l", "kp_r", "off_l", "off_r",
+                                             "width", "height", "max_nq", "max_nt")],
+                            ratio=ratio, want=want)
+        res = torch.empty((max(n_pairs, 1), RESULT_DTYPE.itemsize), dtype=torch.uint8,
+                          device=lefts.device)
+
+        def launch(h, l_ptr, r_ptr, n, W, H, prm, kp, fl, grp, pk, info, st):
+            o = capi.BatchOutputs(res.data_ptr())
+            return self.ctx.L.erp_image_pairs_run(h, l_ptr, r_ptr, n, W, H, prm, kp, fl, grp, pk,
+                                                  ratio, C.byref(self.cfg), C.byref(o), info, st)
+        self.last_packed = ss._image_pairs(lefts, rights, max_kp, fill, max_group_pairs,
+                                           surf_params, launch, "erp_image_pairs_run")
+        self.last_info = ss.last_info
+        return {"results": res[:n_pairs]}
 
     def _launch(self, b, ratio, outs, stream, dev):
         import torch

@@ -95,7 +95,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_surf_detect_compute_dev", "erp_epipolar_draw_dev", "erp_draw_match_dev",
             "erp_random_shuffle_prefix", "erp_ctx_set_graphs", "erp_debug_check_pads", "erp_debug_lip_counters",
             "erp_debug_snapshot", "erp_ctx_set_option", "erp_ctx_get_option",
-            "erp_debug_set_alloc_pad"]
+            "erp_debug_set_alloc_pad", "erp_pack_band_features_dev",
+            "erp_image_pairs_features_dev", "erp_image_pairs_run"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -112,6 +113,20 @@ class SurfParams(C.Structure):
     _fields_ = [("hessian_threshold", C.c_double), ("n_octaves", C.c_int32),
                 ("n_octave_layers", C.c_int32), ("extended", C.c_int32), ("upright", C.c_int32)]
 
+
+class PackedPairs(C.Structure):
+    _fields_ = [("desc_l", P), ("desc_r", P), ("kp_l", P), ("kp_r", P), ("off_l", P), ("off_r", P),
+                ("width", P), ("height", P), ("band_counts", P), ("cap_l", C.c_int64),
+                ("cap_r", C.c_int64)]
+
+
+class ImageBatchInfo(C.Structure):
+    _fields_ = [("need_kp", C.c_int32), ("max_nq", C.c_int32), ("max_nt", C.c_int32),
+                ("groups", C.c_int32), ("fits", C.c_int32), ("reserved", C.c_int32),
+                ("rows_l", C.c_int64), ("rows_r", C.c_int64)]
+
+
+assert C.sizeof(PackedPairs) == 88 and C.sizeof(ImageBatchInfo) == 40
 
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -208,6 +223,16 @@ def load(build_if_missing: bool = False):
                                         C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, P, P, P, P]
     L.erp_draw_match_dev.argtypes = [P, P, P, C.c_int32, C.c_int32, P, P, C.c_int32, P, P]
     L.erp_random_shuffle_prefix.argtypes = [C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, P]
+    L.erp_pack_band_features_dev.argtypes = [P, P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.POINTER(PackedPairs), P]
+    L.erp_image_pairs_features_dev.argtypes = [P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(SurfParams), C.c_int32, C.c_int32,
+                                               C.c_int32, C.POINTER(PackedPairs),
+                                               C.POINTER(ImageBatchInfo), P]
+    L.erp_image_pairs_run.argtypes = [P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(SurfParams), C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(PackedPairs), C.c_float, C.POINTER(RansacCfg),
+                                      C.POINTER(BatchOutputs), C.POINTER(ImageBatchInfo), P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]

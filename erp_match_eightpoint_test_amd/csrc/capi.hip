@@ -124,7 +124,7 @@ struct erp_ctx {
     DevBuf part, part1, pu, ccount, cand, bsel, edges, gfin, matches, counts, flags, pts, polyR, polyQ, idx, gram, hyps, rv, tv, kcount, tmean,
         sortbuf, w0, off, wh, results, in_a, in_b, in_c, in_d, dscale, lb, ub, surv, nsurv, wins,
         rtab, limbs, tsplit, ovf, remap_scr, vchunk, lipref, inl, hlite;
-    DevBuf extra[13];         // erp_ctx_scratch_internal slots (1-11 SURF, 12 viz)
+    DevBuf extra[18];         // erp_ctx_scratch_internal slots (1-11 SURF, 12 viz, 13-17 image batch)
     // route options (erp_ctx_set_option; include/erp_match.h documents each, defaults below)
     int32_t opt[ERP_OPT_COUNT] = {
         -1,  // SMALL_BATCH: auto

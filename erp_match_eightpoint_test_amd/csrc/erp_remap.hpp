@@ -6,6 +6,9 @@
 #include <stdint.h>
 
 #include "../../include/erp_match.h"
+#ifdef __HIPCC__
+#include "erp_device.hpp"
+#endif
 
 namespace erp {
 
@@ -51,5 +54,37 @@ struct BandKeypointArgs {
     int32_t W, H;
 };
 hipError_t launch_band_keypoints(erp_point2f* d_kp, const BandKeypointArgs& a, hipStream_t st);
+
+#ifdef __HIPCC__
+// do_all's un-rotation of one band keypoint (src/spherical_surf.cpp:120-133): the unrotated
+// band shifts pt.y by height*3/8 (float); the others go through rotate_keypoint with the
+// band's pitch matrix m (offset_i = pt.y + height*3/8 in float, truncated; col = (int)pt.x).
+// Shared by band_keypoints_kernel (remap.hip) and the batch pack kernel (image_batch.hip).
+__device__ __forceinline__ erp_point2f unrotate_band_keypoint(erp_point2f p, bool shift,
+                                                              const double* m, int32_t W,
+                                                              int32_t H) {
+    const float off = (float)(H * 3 / 8);
+    if (shift) {
+        p.y = p.y + off;
+    } else {
+        const int32_t oi = trunc_i32_x86f(p.y + off);
+        const int32_t ci = trunc_i32_x86f(p.x);
+        int32_t r, c;
+        rotate_pixel(oi, ci, m, W, H, &r, &c);
+        p.x = (float)c;
+        p.y = (float)r;
+    }
+    return p;
+}
+#endif
+
+// the pitch matrix rotate_keypoint / crop_rotated_image build from a float pitch in degrees
+// (remap_api.hip)
+void pitch_matrix(float deg, double m[9]);
+// erp_spherical_bands_dev's launches without its argument checks and call section (the caller
+// holds the context's): image i's four bands go to d_bands + i * band_set_stride bytes
+erp_status spherical_bands_enqueue(erp_ctx* ctx, const uint8_t* d_ims, int32_t n_images,
+                                   int32_t W, int32_t H, uint8_t* d_bands,
+                                   size_t band_set_stride, hipStream_t st);
 
 }  // namespace erp

@@ -89,4 +89,18 @@ hipError_t launch_surf_describe(const uint8_t* images, int n_images, int W, int 
 hipError_t launch_surf_compact(int n_images, const SurfScratch& scr, int max_kp, erp_keypoint* kp_out,
                                float* desc_out, int32_t* counts, hipStream_t st);
 
+
+// surf_api.hip.  The argument check of erp_surf_detect_compute_dev, the device bytes one more
+// image adds to its scratch, and its launches without the argument checks and the context's
+// call section (the caller holds it).  *h_raw_max (optional) is raised to the largest raw count.
+bool surf_args_ok(int32_t W, int32_t H, int32_t channels, const erp_surf_params* prm,
+                  int32_t max_kp);
+size_t surf_scratch_bytes_per_image(int32_t W, int32_t H, int32_t channels,
+                                    const erp_surf_params* prm, int32_t max_kp);
+erp_status surf_detect_compute_enqueue(erp_ctx* ctx, const uint8_t* d_images, int32_t n_images,
+                                       int32_t W, int32_t H, int32_t channels,
+                                       const erp_surf_params* prm, int32_t max_kp,
+                                       erp_keypoint* d_kp, float* d_desc, int32_t* d_count,
+                                       hipStream_t st, int32_t* h_raw_max);
+
 }  // namespace erp

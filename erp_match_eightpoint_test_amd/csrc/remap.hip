@@ -142,19 +142,7 @@ __global__ __launch_bounds__(256) void band_keypoints_kernel(erp_point2f* __rest
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.end[3]) return;
     const int band = (i >= a.end[0]) + (i >= a.end[1]) + (i >= a.end[2]);
-    erp_point2f p = kp[i];
-    const float off = (float)(a.H * 3 / 8);
-    if (band == a.shift_band) {
-        p.y = p.y + off;
-    } else {
-        const int32_t oi = trunc_i32_x86f(p.y + off);
-        const int32_t ci = trunc_i32_x86f(p.x);
-        int32_t r, c;
-        rotate_pixel(oi, ci, a.m[band], a.W, a.H, &r, &c);
-        p.x = (float)c;
-        p.y = (float)r;
-    }
-    kp[i] = p;
+    kp[i] = unrotate_band_keypoint(kp[i], band == a.shift_band, a.m[band], a.W, a.H);
 }
 
 }  // namespace

@@ -43,11 +43,6 @@ void gemm33(const double* a, const double* b, double* d) {
 // M_PI*(x)/180.0 in double, rounded to float, widened back by eular2rot(Vec3d)
 double rad_f(float deg) { return (double)(float)(erp::kPi * (double)deg / 180.0); }
 
-void pitch_matrix(float deg, double m[9]) {
-    const double th[3] = {0.0, rad_f(deg), 0.0};
-    erp_eular2rot(th, m);
-}
-
 erp_status set_dev(erp_ctx* ctx) {
     if (!ctx) return ERP_INVALID_ARG;
     return hipSetDevice(erp_ctx_device_internal(ctx)) == hipSuccess ? ERP_OK : ERP_HIP_ERROR;
@@ -67,6 +62,46 @@ bool dims_ok(int32_t W, int32_t H) {
 }
 
 }  // namespace
+
+namespace erp {
+void pitch_matrix(float deg, double m[9]) {
+    const double th[3] = {0.0, rad_f(deg), 0.0};
+    erp_eular2rot(th, m);
+}
+}  // namespace erp
+using erp::pitch_matrix;
+
+namespace erp {
+erp_status spherical_bands_enqueue(erp_ctx* ctx, const uint8_t* d_ims, int32_t n_images,
+                                   int32_t W, int32_t H, uint8_t* d_bands,
+                                   size_t band_set_stride, hipStream_t st) {
+    erp::RemapScratch scr;
+    if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
+    static const float pitch[4] = {45.f, 0.f, -45.f, -90.f};  // do_all :77-83 (n1 unrotated)
+    double pm[4][9];
+    for (int b = 0; b < 4; b++)
+        if (b != 1) pitch_matrix(pitch[b], pm[b]);
+    const size_t img = (size_t)W * H * 3, band = (size_t)(H / 4) * W * 3;
+    constexpr int per = erp::kMaxRemapJobs / 4;  // images per launch
+    for (int i0 = 0; i0 < n_images; i0 += per) {
+        erp::RemapJobs jobs{};
+        int n = 0;
+        for (int i = i0; i < std::min(n_images, i0 + per); i++)
+            for (int b = 0; b < 4; b++, n++) {
+                erp::RemapJob& j = jobs.j[n];
+                j.src = d_ims + (size_t)i * img;
+                j.dst = d_bands + (size_t)i * band_set_stride + (size_t)b * band;
+                if (b != 1) memcpy(j.m, pm[b], sizeof(j.m));
+                j.row0 = H * 3 / 8;
+                j.rows = H / 4;
+                j.mode = b == 1 ? erp::kRemapCopy : erp::kRemapCrop;
+            }
+        if (erp::launch_remap(jobs, n, H / 4, W, W, H, scr, st) != hipSuccess)
+            return ERP_HIP_ERROR;
+    }
+    return ERP_OK;
+}
+}  // namespace erp
 
 extern "C" {
 
@@ -171,31 +206,8 @@ erp_status erp_spherical_bands_dev(erp_ctx* ctx, const uint8_t* d_ims, int32_t n
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
     CtxCallGuard call(ctx, (hipStream_t)stream);
-    erp::RemapScratch scr;
-    if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
-    static const float pitch[4] = {45.f, 0.f, -45.f, -90.f};  // do_all :77-83 (n1 unrotated)
-    double pm[4][9];
-    for (int b = 0; b < 4; b++)
-        if (b != 1) pitch_matrix(pitch[b], pm[b]);
-    const size_t img = (size_t)W * H * 3, band = (size_t)(H / 4) * W * 3;
-    constexpr int per = erp::kMaxRemapJobs / 4;  // images per launch
-    for (int i0 = 0; i0 < n_images; i0 += per) {
-        erp::RemapJobs jobs{};
-        int n = 0;
-        for (int i = i0; i < std::min(n_images, i0 + per); i++)
-            for (int b = 0; b < 4; b++, n++) {
-                erp::RemapJob& j = jobs.j[n];
-                j.src = d_ims + (size_t)i * img;
-                j.dst = d_bands + ((size_t)i * 4 + b) * band;
-                if (b != 1) memcpy(j.m, pm[b], sizeof(j.m));
-                j.row0 = H * 3 / 8;
-                j.rows = H / 4;
-                j.mode = b == 1 ? erp::kRemapCopy : erp::kRemapCrop;
-            }
-        if (erp::launch_remap(jobs, n, H / 4, W, W, H, scr, (hipStream_t)stream) != hipSuccess)
-            return ERP_HIP_ERROR;
-    }
-    return ERP_OK;
+    return erp::spherical_bands_enqueue(ctx, d_ims, n_images, W, H, d_bands,
+                                        (size_t)4 * (H / 4) * W * 3, (hipStream_t)stream);
 }
 
 erp_status erp_rotate_keypoints_dev(erp_ctx* ctx, erp_point2f* d_kp, int32_t n, float pitch_deg,

@@ -70,32 +70,32 @@ void gaussian(int n, double sigma, float* cf) {
 
 }  // namespace
 
-extern "C" {
+namespace erp {
 
-void erp_surf_params_default(erp_surf_params* p) {
-    if (!p) return;
-    p->hessian_threshold = 100;
-    p->n_octaves = 4;
-    p->n_octave_layers = 3;
-    p->extended = 0;
-    p->upright = 0;
+bool surf_args_ok(int32_t W, int32_t H, int32_t channels, const erp_surf_params* prm,
+                  int32_t max_kp) {
+    return prm && W >= 1 && H >= 1 && (channels == 1 || channels == 3) && max_kp >= 1 &&
+           prm->extended == 0 && prm->upright == 0 && prm->n_octaves >= 1 &&
+           prm->n_octaves <= 8 && prm->n_octave_layers >= 1 && prm->n_octave_layers <= 8 &&
+           (int64_t)(W + 1) * (H + 1) * 255 < ((int64_t)1 << 31);  // CV_32S integral image
 }
 
-erp_status erp_surf_detect_compute_dev(erp_ctx* ctx, const uint8_t* d_images, int32_t n_images,
+// the per-image buffers surf_detect_compute_enqueue sizes below (gray, sum, det, raw, sorted,
+// desc); the descriptor pass's chunk pool (<= 1 GiB) does not grow with the image count
+size_t surf_scratch_bytes_per_image(int32_t W, int32_t H, int32_t channels,
+                                    const erp_surf_params* prm, int32_t max_kp) {
+    size_t det = 0;
+    for (int o = 0; o < prm->n_octaves; o++)
+        det += (size_t)(prm->n_octave_layers + 2) * (size_t)(H >> o) * (size_t)(W >> o);
+    return (channels == 3 ? (size_t)W * H : 0) + (size_t)(W + 1) * (H + 1) * 4 +
+           std::max<size_t>(det, 1) * 4 + (size_t)max_kp * (2 * sizeof(erp_keypoint) + 64 * 4);
+}
+
+erp_status surf_detect_compute_enqueue(erp_ctx* ctx, const uint8_t* d_images, int32_t n_images,
                                        int32_t W, int32_t H, int32_t channels,
                                        const erp_surf_params* prm, int32_t max_kp,
                                        erp_keypoint* d_kp, float* d_desc, int32_t* d_count,
-                                       void* stream) {
-    if (!ctx || !prm || n_images < 0 || W < 1 || H < 1 || (channels != 1 && channels != 3) ||
-        max_kp < 1 || prm->extended != 0 || prm->upright != 0 || prm->n_octaves < 1 ||
-        prm->n_octaves > 8 || prm->n_octave_layers < 1 || prm->n_octave_layers > 8 ||
-        (int64_t)(W + 1) * (H + 1) * 255 >= ((int64_t)1 << 31))  // CV_32S integral image
-        return ERP_INVALID_ARG;
-    if (n_images == 0) return ERP_OK;
-    if (!d_images || !d_kp || !d_desc || !d_count) return ERP_INVALID_ARG;
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
-    hipStream_t st = (hipStream_t)stream;
-    CtxCallGuard call(ctx, st);
+                                       hipStream_t st, int32_t* h_raw_max) {
     const int nO = prm->n_octaves, nL = prm->n_octave_layers, nT = (nL + 2) * nO;
     // layer table (host)
     std::vector<erp::SurfLayer> layers(nT);
@@ -230,6 +230,8 @@ erp_status erp_surf_detect_compute_dev(erp_ctx* ctx, const uint8_t* d_images, in
     if (hipMemcpyAsync(cnt.data(), d_count, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return ERP_HIP_ERROR;
+    if (h_raw_max)
+        for (int i = 0; i < n_images; i++) *h_raw_max = std::max(*h_raw_max, cnt[i]);
     std::vector<int32_t> kpre(n_images + 1, 0);
     for (int i = 0; i < n_images; i++)  // an overflowed image (count < 0) is not described
         kpre[i + 1] = kpre[i] + std::min(std::max(cnt[i], 0), max_kp);
@@ -258,6 +260,35 @@ erp_status erp_surf_detect_compute_dev(erp_ctx* ctx, const uint8_t* d_images, in
     return erp::launch_surf_compact(n_images, scr, max_kp, d_kp, d_desc, d_count, st) == hipSuccess
                ? ERP_OK
                : ERP_HIP_ERROR;
+}
+
+}  // namespace erp
+
+extern "C" {
+
+void erp_surf_params_default(erp_surf_params* p) {
+    if (!p) return;
+    p->hessian_threshold = 100;
+    p->n_octaves = 4;
+    p->n_octave_layers = 3;
+    p->extended = 0;
+    p->upright = 0;
+}
+
+erp_status erp_surf_detect_compute_dev(erp_ctx* ctx, const uint8_t* d_images, int32_t n_images,
+                                       int32_t W, int32_t H, int32_t channels,
+                                       const erp_surf_params* prm, int32_t max_kp,
+                                       erp_keypoint* d_kp, float* d_desc, int32_t* d_count,
+                                       void* stream) {
+    if (!ctx || n_images < 0 || !erp::surf_args_ok(W, H, channels, prm, max_kp))
+        return ERP_INVALID_ARG;
+    if (n_images == 0) return ERP_OK;
+    if (!d_images || !d_kp || !d_desc || !d_count) return ERP_INVALID_ARG;
+    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
+    hipStream_t st = (hipStream_t)stream;
+    CtxCallGuard call(ctx, st);
+    return erp::surf_detect_compute_enqueue(ctx, d_images, n_images, W, H, channels, prm, max_kp,
+                                            d_kp, d_desc, d_count, st, nullptr);
 }
 
 }  // extern "C"

@@ -425,6 +425,79 @@ erp_status erp_surf_detect_compute_dev(erp_ctx* ctx, const uint8_t* d_images, in
                                        erp_keypoint* d_kp, float* d_desc, int32_t* d_count,
                                        void* stream);
 
+/* ---- batched do_all: ERP image pairs -> the packed batch erp_pair_batch_run consumes ----
+   spherical_surf::do_all (src/spherical_surf.cpp:65-179) up to the match, for many pairs at
+   once and without leaving the device: bands (:77-93) -> SURF on every band (:96-118) ->
+   keypoint un-rotation + concatenation n0..n3 (:120-150), written straight into the ragged
+   layout of erp_pair_batch. */
+/* caller-owned device outputs of the pack step; cap_l / cap_r = rows desc_l, kp_l / desc_r,
+   kp_r can hold (rows at or past a capacity are not written).  desc_l / desc_r are 16-byte
+   aligned. */
+typedef struct erp_packed_pairs {
+    float* desc_l;              /* [cap_l][64] */
+    float* desc_r;              /* [cap_r][64] */
+    erp_point2f* kp_l;          /* [cap_l] un-rotated ERP pixels */
+    erp_point2f* kp_r;          /* [cap_r] */
+    int64_t* off_l;             /* [n_pairs+1] */
+    int64_t* off_r;             /* [n_pairs+1] */
+    int32_t* width;             /* [n_pairs] */
+    int32_t* height;            /* [n_pairs] */
+    int32_t* band_counts;       /* [n_pairs][2][4] keypoints per side and band; may be NULL */
+    int64_t cap_l;
+    int64_t cap_r;
+} erp_packed_pairs;
+/* what the host learns from erp_image_pairs_features_dev / erp_image_pairs_run */
+typedef struct erp_image_batch_info {
+    int32_t need_kp;            /* largest raw keypoint count of any band */
+    int32_t max_nq;             /* largest left / right row count of any pair */
+    int32_t max_nt;
+    int32_t groups;             /* groups of pairs the call went through */
+    int32_t fits;               /* 1: the outputs are complete.  0: need_kp > max_kp, or rows_l >
+                                   cap_l, or rows_r > cap_r: the outputs are unspecified; rerun
+                                   with max_kp >= need_kp and capacities >= rows_l / rows_r (a
+                                   band that overflowed max_kp contributes no rows to these) */
+    int32_t reserved;
+    int64_t rows_l;             /* total rows of each side */
+    int64_t rows_r;
+} erp_image_batch_info;
+/* The pack step alone.  d_kp [8 n_pairs][max_kp], d_desc [8 n_pairs][max_kp][64], d_count
+   [8 n_pairs] as erp_surf_detect_compute_dev writes them for the band images in the order
+   [pair][side left, right][band n0..n3] of W x H ERP images (bands H/4 x W).  Per side and pair
+   the rows of bands n0, n1, n2, n3 are concatenated (a count outside [0, max_kp] is clamped
+   into it; rows at or past a count are never read), descriptors copied, keypoints un-rotated
+   as erp_unrotate_band_keypoints_dev does, pairs appended one after another: out->off_l[p] is
+   the first left row of pair p, off_l[n_pairs] the total.  Asynchronous on `stream`. */
+erp_status erp_pack_band_features_dev(erp_ctx* ctx, const erp_keypoint* d_kp, const float* d_desc,
+                                      const int32_t* d_count, int32_t n_pairs, int32_t max_kp,
+                                      int32_t W, int32_t H, const erp_packed_pairs* out,
+                                      void* stream);
+/* d_left / d_right [n_pairs][H][W][3] (BGR, one size per call) -> the packed batch.  The band
+   canvases are pre-filled with the byte `fill` (0 in the reference's Mat::zeros sense; the
+   remap leaves out-of-image pixels unwritten); max_kp = keypoint slots per band.  The pairs
+   go through in groups (bands, SURF on the group's 8 g bands, pack) so that SURF's scratch
+   stays within a fixed budget; max_group_pairs > 0 sets the group size, 0 = the largest that
+   fits the budget.  NOT graph-capturable and not asynchronous: the call synchronises `stream`
+   a fixed few times per group (SURF's counts) and once at the end (the totals for *info),
+   never per pair.  Overflow is reported in info->fits with status ERP_OK. */
+erp_status erp_image_pairs_features_dev(erp_ctx* ctx, const uint8_t* d_left,
+                                        const uint8_t* d_right, int32_t n_pairs, int32_t W,
+                                        int32_t H, const erp_surf_params* params, int32_t max_kp,
+                                        int32_t fill, int32_t max_group_pairs,
+                                        const erp_packed_pairs* out, erp_image_batch_info* info,
+                                        void* stream);
+/* erp_image_pairs_features_dev followed, when info->fits and n_pairs > 0, by
+   erp_pair_batch_run on the packed batch (dim 64, info's max_nq / max_nt): what
+   src/automatic.cpp:117-126 runs per pair, from images to R, T.  Inherits both calls' limits:
+   not graph-capturable; a pair with more than 65535 left rows gives ERP_INVALID_ARG (info is
+   filled first, so max_nq shows why). */
+erp_status erp_image_pairs_run(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                               int32_t n_pairs, int32_t W, int32_t H,
+                               const erp_surf_params* params, int32_t max_kp, int32_t fill,
+                               int32_t max_group_pairs, const erp_packed_pairs* packed,
+                               float ratio, const erp_ransac_cfg* cfg,
+                               const erp_batch_outputs* out, erp_image_batch_info* info,
+                               void* stream);
+
 /* ---- visual outputs, device images ---- */
 /* epipolar_tool (src/epipolar_tool.hpp / .cpp:7-71, constructor + draw_epipole :74-128): n_key
    (<= 7, the reference's color_set) of the m matched pairs (host keypoints, ERP pixels of an
