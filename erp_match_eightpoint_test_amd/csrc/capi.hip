@@ -167,6 +167,27 @@ struct erp_ctx {
     uint64_t w0_offset = 0;
 };
 
+// every named DevBuf of the context (extra[] and snap apart); graph = a captured
+// erp_pair_batch_run bakes its address in (graph_key).  The host-pointer entry points' staging
+// (off, wh, in_a..in_d) and remap_scr are not part of that call.
+struct CtxBuf {
+    DevBuf erp_ctx::*m;
+    bool graph;
+};
+#define ERP_B(name, graph) {&erp_ctx::name, graph}
+const CtxBuf kCtxBufs[] = {
+    ERP_B(mblk, 1), ERP_B(zsel, 1), ERP_B(part, 1), ERP_B(part1, 1), ERP_B(pu, 1),
+    ERP_B(ccount, 1), ERP_B(cand, 1), ERP_B(bsel, 1), ERP_B(edges, 1), ERP_B(gfin, 1),
+    ERP_B(matches, 1), ERP_B(counts, 1), ERP_B(flags, 1), ERP_B(pts, 1), ERP_B(polyR, 1),
+    ERP_B(polyQ, 1), ERP_B(idx, 1), ERP_B(gram, 1), ERP_B(hyps, 1), ERP_B(rv, 1), ERP_B(tv, 1),
+    ERP_B(kcount, 1), ERP_B(tmean, 1), ERP_B(sortbuf, 1), ERP_B(w0, 1), ERP_B(off, 0),
+    ERP_B(wh, 0), ERP_B(results, 1), ERP_B(in_a, 0), ERP_B(in_b, 0), ERP_B(in_c, 0),
+    ERP_B(in_d, 0), ERP_B(dscale, 1), ERP_B(lb, 1), ERP_B(ub, 1), ERP_B(surv, 1),
+    ERP_B(nsurv, 1), ERP_B(wins, 1), ERP_B(rtab, 1), ERP_B(limbs, 1), ERP_B(tsplit, 1),
+    ERP_B(ovf, 1), ERP_B(remap_scr, 0), ERP_B(vchunk, 1), ERP_B(lipref, 1), ERP_B(inl, 1),
+    ERP_B(hlite, 1)};
+#undef ERP_B
+
 #define ERP_CK(x)                                         \
     do {                                                  \
         if ((x) != hipSuccess) return ERP_HIP_ERROR;      \
@@ -318,16 +339,7 @@ erp_status erp_ctx_create(int32_t device, erp_ctx** out) {
 erp_status erp_ctx_destroy(erp_ctx* ctx) {
     if (!ctx) return ERP_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    DevBuf* all[] = {&ctx->mblk, &ctx->zsel, &ctx->part, &ctx->part1, &ctx->pu, &ctx->ccount, &ctx->cand, &ctx->bsel, &ctx->edges, &ctx->gfin,
-                     &ctx->matches,
-                     &ctx->counts, &ctx->flags, &ctx->pts, &ctx->polyR,
-                     &ctx->polyQ, &ctx->idx, &ctx->gram, &ctx->hyps, &ctx->rv, &ctx->tv,
-                     &ctx->kcount, &ctx->tmean, &ctx->sortbuf, &ctx->w0, &ctx->off, &ctx->wh,
-                     &ctx->results, &ctx->in_a, &ctx->in_b, &ctx->in_c, &ctx->in_d,
-                     &ctx->dscale, &ctx->lb, &ctx->ub, &ctx->surv, &ctx->nsurv, &ctx->wins,
-                     &ctx->rtab, &ctx->limbs, &ctx->tsplit, &ctx->ovf, &ctx->remap_scr, &ctx->vchunk,
-                     &ctx->lipref, &ctx->inl, &ctx->hlite};
-    for (DevBuf* b : all) free_buf(*b);
+    for (const CtxBuf& b : kCtxBufs) free_buf(ctx->*b.m);
     for (DevBuf& b : ctx->extra) free_buf(b);
     free_buf(ctx->snap);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -438,6 +450,7 @@ erp_status run_matcher(erp_ctx* ctx, const float* dq, const float* dt, const int
 erp_status ensure_estimator(erp_ctx* c, const erp::BatchShape& sh, const erp_batch_outputs* out) {
     const size_t P = (size_t)sh.n_pairs;
     const size_t nwaves = (size_t)(sh.iters + 63) / 64;
+    const erp::ConsensusLayout L = erp::consensus_layout(sh.n_pairs, sh.iters);
     bool ok = ensure(c->counts, P * 4) && ensure(c->flags, P * 4) &&
               ensure(c->pts, P * (sh.max_nq + 1) * 48) &&
               ensure(c->wins, P * nwaves * 31 * 64 * 4) && ensure(c->polyR, P * 65 * 31 * 4) &&
@@ -445,30 +458,31 @@ erp_status ensure_estimator(erp_ctx* c, const erp::BatchShape& sh, const erp_bat
               ensure(c->idx, P * nwaves * (size_t)sh.sel_words * 64 * 4) &&
               ensure(c->gram, P * sh.iters * 36 * 8) && ensure(c->limbs, erp::gram_limbs_bytes(sh)) &&
               ensure(c->gfin, P * sh.iters * 9 * 8) && ensure(c->rv, P * 6 * sh.iters * 4) &&
-              ensure(c->kcount, P * 4) && ensure(c->sortbuf, P * (size_t)erp::sortbuf_len(sh.iters) * 4) &&
+              ensure(c->kcount, P * 4) && ensure(c->sortbuf, L.sortbuf.bytes) &&
               ensure(c->w0, 31 * 4) && ensure(c->results, P * sizeof(erp_pair_result)) &&
-              ensure(c->dscale, P * 4) && ensure(c->lb, P * 2 * sh.iters * 8) &&
-              ensure(c->ub, P * 2 * sh.iters * 8) && ensure(c->surv, P * 2 * sh.iters * 4) &&
-              ensure(c->bsel, P * 2 * sh.iters * 8) && ensure(c->zsel, P * 2 * sh.iters * 8) &&
-              ensure(c->lipref, erp::lipref_bytes((int)P, 2 * sh.iters)) && ensure(c->edges, erp::consensus_edges_bytes((int)P)) &&
-              ensure(c->nsurv, P * 20 + 8) && ensure(c->vchunk, erp::valid_chunk_bytes(sh));
+              ensure(c->dscale, P * 4) && ensure(c->lb, L.lb_bytes) && ensure(c->ub, L.ub_bytes) &&
+              ensure(c->surv, L.surv_bytes) && ensure(c->bsel, L.bsel_bytes) &&
+              ensure(c->zsel, L.zsel_bytes) && ensure(c->lipref, L.lipref.bytes) &&
+              ensure(c->edges, L.edges.bytes) && ensure(c->nsurv, L.counts.bytes) &&
+              ensure(c->vchunk, erp::valid_chunk_bytes(sh));
     if (ok && !(out && out->hyps)) ok = ensure(c->hyps, P * sh.iters * sizeof(erp_hypothesis));
-    if (ok) ok = ensure(c->hlite, erp::hyp_lite_bytes(sh));
+    if (ok) ok = ensure(c->hlite, L.hlite.bytes);
     if (ok && !(out && out->tvec)) ok = ensure(c->tv, P * 6 * sh.iters * 4);
     if (ok && !(out && out->dist)) ok = ensure(c->tmean, P * 2 * sh.iters * 8);
     if (!ok) return ERP_OUT_OF_MEMORY;
     if (!c->rtab_valid) {  // once per context: the reciprocal table, verified exactly
         constexpr int n = erp::kRecipTable;
-        if (!ensure(c->rtab, erp::kRecipTableBytes)) return ERP_OUT_OF_MEMORY;
+        if (!ensure(c->rtab, L.rtab.bytes)) return ERP_OUT_OF_MEMORY;
         {  // the magic-number table after it (the sampler's d >= 256 quotients)
             std::vector<uint64_t> mt(n);
             if (!erp::build_magic_table(mt.data(), n)) return ERP_INTERNAL;
-            ERP_CK(hipMemcpy((double*)c->rtab.p + n, mt.data(), (size_t)n * 8,
-                             hipMemcpyHostToDevice));
+            ERP_CK(hipMemcpy(erp::ws_at<uint64_t>(c->rtab.p, L.rtab.magic), mt.data(),
+                             (size_t)n * 8, hipMemcpyHostToDevice));
         }
-        int32_t* d_bad = (int32_t*)((char*)c->rtab.p + (size_t)n * 16);
+        int32_t* d_bad = erp::ws_at<int32_t>(c->rtab.p, L.rtab.bad);
         ERP_CK(hipMemset(d_bad, 0, 4));
-        ERP_CK(erp::launch_recip_table(n, (double*)c->rtab.p, d_bad, nullptr));
+        ERP_CK(erp::launch_recip_table(n, erp::ws_at<double>(c->rtab.p, L.rtab.recip), d_bad,
+                                       nullptr));
         int32_t bad = 0;
         ERP_CK(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
         if (bad) return ERP_INTERNAL;
@@ -528,11 +542,6 @@ erp_status run_inliers(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_c
 bool use_lite(const erp_ransac_cfg* cfg, const erp_batch_outputs* out) {
     return !(out && out->hyps) && !(cfg->inlier_thr > 0.0f) && ERP_FUSE_EIGEN != 2;
 }
-float* lite_hl(erp_ctx* c) { return (float*)c->hlite.p; }
-int32_t* lite_wsum(erp_ctx* c, const erp::BatchShape& sh) {
-    return (int32_t*)(lite_hl(c) + (size_t)sh.n_pairs * 9 * sh.iters);
-}
-
 // estimator stages after counts/pts are in place (lite: the estimates in the lite layout)
 erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ransac_cfg* cfg,
                           const erp_batch_outputs* out, hipStream_t st, bool lite = false) {
@@ -544,44 +553,32 @@ erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ra
     auto* counts = (int32_t*)c->counts.p;
     auto* flags = (int32_t*)c->flags.p;
     auto* hyps = (out && out->hyps) ? out->hyps : (erp_hypothesis*)c->hyps.p;
+    const erp::ConsensusLayout L = erp::consensus_layout(sh.n_pairs, sh.iters);
     if (cfg->sampler == ERP_SAMPLER_PHILOX) {  // counter-based: no jump polynomials / windows
         if (c->opt[ERP_OPT_DEBUG_STAGES] & 4) {
             StageTimer _t(ctx, ERP_STAGE_SAMPLER, st);
             ERP_CK(erp::launch_philox_sampler(counts, sh, cfg->sample_frac, cfg->seed, cfg->offset,
                                               sh.max_nq, (uint32_t*)c->idx.p, flags, st));
         }
-        if (c->opt[ERP_OPT_DEBUG_STAGES] & 8) {
-            StageTimer _t(ctx, ERP_STAGE_GRAM, st);
-            ERP_CK(erp::launch_gram_mfma(counts, (double*)c->pts.p, (uint32_t*)c->idx.p, sh,
-                                         cfg->sample_frac, (int8_t*)c->limbs.p, (double*)c->gram.p,
-                                         out ? out->samples : nullptr,
-                                         ERP_FUSE_EIGEN ? (double*)c->gfin.p : nullptr,
-                                         ERP_FUSE_EIGEN == 2 ? hyps : nullptr, cfg->valid_abs, st));
+    } else {
+        const double* rtab = erp::ws_at<double>(c->rtab.p, L.rtab.recip);
+        if (c->opt[ERP_OPT_DEBUG_STAGES] & 2) {
+            StageTimer _t(ctx, ERP_STAGE_JUMP_PREP, st);
+            ERP_CK(erp::launch_jump_prep(counts, sh, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p,
+                                         st));
         }
-        if (c->opt[ERP_OPT_DEBUG_STAGES] & 32) {
-            StageTimer _t(ctx, ERP_STAGE_EIGEN, st);
-            ERP_CK(erp::launch_eigen(counts, (double*)c->gram.p, sh, cfg->sample_frac,
-                                     cfg->valid_abs, (double*)c->gfin.p, hyps, st, ERP_FUSE_EIGEN,
-                                     want_e(cfg, out), lite ? lite_hl(c) : nullptr,
-                                     lite ? lite_wsum(c, sh) : nullptr));
+        if (c->opt[ERP_OPT_DEBUG_STAGES] & 2) {
+            StageTimer _t(ctx, ERP_STAGE_WINDOWS, st);
+            ERP_CK(erp::launch_sampler(counts, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p,
+                                       (uint32_t*)c->w0.p, sh, cfg->sample_frac, rtab,
+                                       (uint32_t*)c->wins.p, (uint32_t*)c->idx.p, flags, st, 0));
         }
-        return run_inliers(c, sh, cfg, hyps, st);
-    }
-    if (c->opt[ERP_OPT_DEBUG_STAGES] & 2) {
-        StageTimer _t(ctx, ERP_STAGE_JUMP_PREP, st);
-        ERP_CK(erp::launch_jump_prep(counts, sh, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p, st));
-    }
-    if (c->opt[ERP_OPT_DEBUG_STAGES] & 2) {
-        StageTimer _t(ctx, ERP_STAGE_WINDOWS, st);
-        ERP_CK(erp::launch_sampler(counts, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p,
-                                   (uint32_t*)c->w0.p, sh, cfg->sample_frac, (double*)c->rtab.p,
-                                   (uint32_t*)c->wins.p, (uint32_t*)c->idx.p, flags, st, 0));
-    }
-    if (c->opt[ERP_OPT_DEBUG_STAGES] & 4) {
-        StageTimer _t(ctx, ERP_STAGE_SAMPLER, st);
-        ERP_CK(erp::launch_sampler(counts, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p,
-                                   (uint32_t*)c->w0.p, sh, cfg->sample_frac, (double*)c->rtab.p,
-                                   (uint32_t*)c->wins.p, (uint32_t*)c->idx.p, flags, st, 1));
+        if (c->opt[ERP_OPT_DEBUG_STAGES] & 4) {
+            StageTimer _t(ctx, ERP_STAGE_SAMPLER, st);
+            ERP_CK(erp::launch_sampler(counts, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p,
+                                       (uint32_t*)c->w0.p, sh, cfg->sample_frac, rtab,
+                                       (uint32_t*)c->wins.p, (uint32_t*)c->idx.p, flags, st, 1));
+        }
     }
     if (c->opt[ERP_OPT_DEBUG_STAGES] & 8) {
         StageTimer _t(ctx, ERP_STAGE_GRAM, st);
@@ -595,8 +592,9 @@ erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ra
         StageTimer _t(ctx, ERP_STAGE_EIGEN, st);
         ERP_CK(erp::launch_eigen(counts, (double*)c->gram.p, sh, cfg->sample_frac,
                                  cfg->valid_abs, (double*)c->gfin.p, hyps, st, ERP_FUSE_EIGEN,
-                                 want_e(cfg, out), lite ? lite_hl(c) : nullptr,
-                                 lite ? lite_wsum(c, sh) : nullptr));
+                                 want_e(cfg, out),
+                                 lite ? erp::ws_at<float>(c->hlite.p, L.hlite.hl) : nullptr,
+                                 lite ? erp::ws_at<int32_t>(c->hlite.p, L.hlite.wsum) : nullptr));
     }
     return run_inliers(c, sh, cfg, hyps, st);
 }
@@ -630,27 +628,27 @@ erp_status run_consensus(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac
                          double* lb_ = nullptr, double* ub_ = nullptr, int32_t* bsel_ = nullptr,
                          bool lite = false) {
     erp_ctx* ctx = c;
-    double* lbp = lb_ ? lb_ : (double*)c->lb.p;
-    double* ubp = ub_ ? ub_ : (double*)c->ub.p;
-    int32_t* bselp = bsel_ ? bsel_ : (int32_t*)c->bsel.p;
-    auto* counts = from_hyps ? (int32_t*)c->counts.p : nullptr;
-    auto* flags = (int32_t*)c->flags.p;  // consensus-only: set by consensus_input (non-finite)
+    erp::ConsensusBufs cb{};
+    cb.counts = from_hyps ? (int32_t*)c->counts.p : nullptr;
+    cb.flags = (int32_t*)c->flags.p;  // consensus-only: set by consensus_input (non-finite)
+    cb.kcount = (int32_t*)c->kcount.p;
+    cb.rv = (float*)c->rv.p;
+    cb.tv = (out && out->tvec) ? out->tvec : (float*)c->tv.p;
+    cb.rv_aos = out ? out->rvec : nullptr;
+    cb.dscale = (float*)c->dscale.p;
+    cb.tmean = (out && out->dist) ? out->dist : (double*)c->tmean.p;
+    cb.lb = lb_ ? lb_ : (double*)c->lb.p;
+    cb.ub = ub_ ? ub_ : (double*)c->ub.p;
+    cb.bsel = bsel_ ? bsel_ : (int32_t*)c->bsel.p;
+    cb.zsel = c->zsel.p;
+    cb.surv = c->surv.p;
+    cb.nsurv = c->nsurv.p;
+    cb.edges = c->edges.p;
+    cb.lipref = c->lipref.p;
+    cb.sortbuf = c->sortbuf.p;
+    cb.hlite = c->hlite.p;
+    cb.results = results;
     auto* hyps = (out && out->hyps) ? out->hyps : (erp_hypothesis*)c->hyps.p;
-    auto* tv = (out && out->tvec) ? out->tvec : (float*)c->tv.p;
-    auto* tmean = (out && out->dist) ? out->dist : (double*)c->tmean.p;
-    if (from_hyps && phase != 2 && lite) {
-        StageTimer _t(ctx, ERP_STAGE_VALID_COMPACT, st);
-        ERP_CK(erp::launch_valid_place(counts, lite_hl(c), lite_wsum(c, sh), sh, cfg->sample_frac,
-                                       (float*)c->rv.p, tv, (int32_t*)c->kcount.p,
-                                       out ? out->rvec : nullptr, (float*)c->dscale.p,
-                                       (float*)c->edges.p, st));
-    } else if (from_hyps && phase != 2) {
-        StageTimer _t(ctx, ERP_STAGE_VALID_COMPACT, st);
-        ERP_CK(erp::launch_valid_compact(counts, hyps, sh, cfg->sample_frac,
-                                         (int32_t*)c->vchunk.p, (float*)c->rv.p, tv,
-                                         (int32_t*)c->kcount.p, out ? out->rvec : nullptr,
-                                         (float*)c->dscale.p, st));
-    }
     // small batches (the single-pair call of src/automatic.cpp:117-126): every row gets its
     // K-column histogram, no Lipschitz pre-pruning, no zoom or refine stage.  For one pair at
     // 10k iterations that pass is ~25-35 us of the whole GPU, against ~20 dependent small
@@ -665,44 +663,33 @@ erp_status run_consensus(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac
                        (sb >= 0 ? sh.n_pairs <= sb : sh.n_pairs * kk * kk <= 2e9);
     const bool prune = !small;
     const PruningOpts po = pruning_opts(c, sh);
+    const erp::ConsensusParams cp{cfg->sample_frac, cfg->trim_lo, cfg->trim_hi, shard, nshards,
+                                  prune, po.lip2, po.lipg, po.flat_pct, po.hint,
+                                  from_hyps && lite};  // (valid_place wrote the edges)
+    if (from_hyps && phase != 2 && lite) {
+        StageTimer _t(ctx, ERP_STAGE_VALID_COMPACT, st);
+        ERP_CK(erp::launch_valid_place(cb, sh, cp, st));
+    } else if (from_hyps && phase != 2) {
+        StageTimer _t(ctx, ERP_STAGE_VALID_COMPACT, st);
+        ERP_CK(erp::launch_valid_compact(cb.counts, hyps, sh, cfg->sample_frac,
+                                         (int32_t*)c->vchunk.p, cb.rv, cb.tv, cb.kcount,
+                                         cb.rv_aos, cb.dscale, st));
+    }
     if (phase != 2) {
         StageTimer _t(ctx, ERP_STAGE_CONSENSUS_BOUNDS, st);
-        ERP_CK(erp::launch_consensus_bounds((int32_t*)c->kcount.p, (float*)c->rv.p,
-                                            (float*)c->dscale.p, (float*)c->edges.p, sh,
-                                            cfg->trim_lo, cfg->trim_hi, lbp, ubp, bselp, shard,
-                                            nshards, prune ? (int32_t*)c->surv.p : nullptr,
-                                            prune ? (int32_t*)c->nsurv.p + sh.n_pairs : nullptr,
-                                            (int32_t*)c->zsel.p, po.lip2,
-                                            (int32_t*)c->sortbuf.p, c->lipref.p, po.lipg,
-                                            po.flat_pct, po.hint, st,
-                                            from_hyps && lite));  // (valid_place wrote the edges)
+        ERP_CK(erp::launch_consensus_bounds(cb, sh, cp, st));
     }
     if (c->opt[ERP_OPT_DEBUG_SNAP] && phase == 0) {
-        const size_t nrow = (size_t)sh.n_pairs * 2 * sh.iters;
-        // (kernels.hip lipref_cap at the default second-stage step 4)
-        const size_t lrb = (size_t)sh.n_pairs * (2 * sh.iters / 4 + 64) * 16 + (size_t)sh.n_pairs * 12;
-        c->snap_bytes = nrow * 16 + (size_t)sh.n_pairs * 4 + lrb;
+        c->snap_bytes = erp::consensus_snapshot_bytes(sh);
         if (!ensure(c->snap, c->snap_bytes)) return ERP_OUT_OF_MEMORY;
-        ERP_CK(hipMemcpyAsync(c->snap.p, lbp, nrow * 8, hipMemcpyDeviceToDevice, st));
-        ERP_CK(hipMemcpyAsync((char*)c->snap.p + nrow * 8, ubp, nrow * 8, hipMemcpyDeviceToDevice, st));
-        if (prune)
-            ERP_CK(hipMemcpyAsync((char*)c->snap.p + nrow * 16, (int32_t*)c->nsurv.p + sh.n_pairs,
-                                  (size_t)sh.n_pairs * 4, hipMemcpyDeviceToDevice, st));
-        else  // (the small-batch route lists nothing: -1 = every row binned)
-            ERP_CK(hipMemsetAsync((char*)c->snap.p + nrow * 16, 0xFF, (size_t)sh.n_pairs * 4, st));
-        // + the first-stage references (float4 [P][cap]), their U [P] f64 and counts [P] i32
-        ERP_CK(hipMemcpyAsync((char*)c->snap.p + nrow * 16 + (size_t)sh.n_pairs * 4, c->lipref.p, lrb,
-                              hipMemcpyDeviceToDevice, st));
+        ERP_CK(erp::consensus_snapshot(cb, sh, cp, c->snap.p, st));
     }
     if (phase == 1) return ERP_OK;
     if (phase == 2)  // the bounds ran per shard (binned rows not combined): report -1
-        ERP_CK(hipMemsetAsync((int32_t*)c->nsurv.p + sh.n_pairs, 0xFF, sizeof(int32_t) * sh.n_pairs, st));
+        ERP_CK(erp::consensus_mark_unbinned(cb, sh, st));
     {
         StageTimer _t(ctx, ERP_STAGE_CONSENSUS_SELECT, st);
-        ERP_CK(erp::launch_consensus_select((int32_t*)c->kcount.p, lbp,
-                                            ubp, sh, cfg->trim_lo, cfg->trim_hi,
-                                            (int32_t*)c->surv.p, (int32_t*)c->nsurv.p, tmean, 0,
-                                            st));
+        ERP_CK(erp::launch_consensus_select(cb, sh, cp, 0, st));
     }
     // small batches skip the zoom too: the exact pass takes the first selection's survivors
     // (~150 for a typical pair, one grid-wide launch); single pair 0.487 -> 0.437 ms
@@ -711,50 +698,28 @@ erp_status run_consensus(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac
     for (int level = 1; level <= zoom_levels; level++) {
         {
             StageTimer _t(ctx, ERP_STAGE_CONSENSUS_BOUNDS, st);
-            ERP_CK(erp::launch_consensus_zoom((int32_t*)c->kcount.p, (float*)c->rv.p,
-                                              (float*)c->dscale.p, (float*)c->edges.p, sh,
-                                              cfg->trim_lo, cfg->trim_hi, lbp, ubp, bselp,
-                                              (int32_t*)c->surv.p, (int32_t*)c->nsurv.p,
-                                              (int32_t*)c->zsel.p, level, st));
+            ERP_CK(erp::launch_consensus_zoom(cb, sh, cp, level, st));
         }
         StageTimer _t(ctx, ERP_STAGE_CONSENSUS_SELECT, st);
-        ERP_CK(erp::launch_consensus_select((int32_t*)c->kcount.p, lbp,
-                                            ubp, sh, cfg->trim_lo, cfg->trim_hi,
-                                            (int32_t*)c->surv.p, (int32_t*)c->nsurv.p, tmean, 0,
-                                            st));
+        ERP_CK(erp::launch_consensus_select(cb, sh, cp, 0, st));
     }
     // (small batches: no refine stage either -- the exact pass takes the survivors in one
     // grid-wide launch; the refine stage's ~8 dependent launches cost a single pair more)
     if (prune) {
         StageTimer _t(ctx, ERP_STAGE_CONSENSUS_REFINE, st);
-        ERP_CK(erp::launch_consensus_refine((int32_t*)c->kcount.p, (float*)c->rv.p,
-                                            (float*)c->dscale.p, sh, cfg->trim_lo, cfg->trim_hi,
-                                            (int32_t*)c->surv.p, (int32_t*)c->nsurv.p,
-                                            bselp, lbp,
-                                            ubp, (int32_t*)c->sortbuf.p, c->lipref.p,
-                                            po.hint, st));
+        ERP_CK(erp::launch_consensus_refine(cb, sh, cp, st));
     }
     if (prune) {
         StageTimer _t(ctx, ERP_STAGE_CONSENSUS_SELECT, st);
-        ERP_CK(erp::launch_consensus_select((int32_t*)c->kcount.p, lbp,
-                                            ubp, sh, cfg->trim_lo, cfg->trim_hi,
-                                            (int32_t*)c->surv.p, (int32_t*)c->nsurv.p, tmean, 1,
-                                            st));
+        ERP_CK(erp::launch_consensus_select(cb, sh, cp, 1, st));
     }
     {
         StageTimer _t(ctx, ERP_STAGE_CONSENSUS_ROWS, st);
-        ERP_CK(erp::launch_consensus_rows((int32_t*)c->kcount.p, (float*)c->rv.p,
-                                          (float*)c->dscale.p, sh, cfg->trim_lo, cfg->trim_hi,
-                                          (int32_t*)c->surv.p, (int32_t*)c->nsurv.p,
-                                          bselp, tmean, st));
+        ERP_CK(erp::launch_consensus_rows(cb, sh, cp, st));
     }
     {
         StageTimer _t(ctx, ERP_STAGE_CONSENSUS_FINAL, st);
-        ERP_CK(erp::launch_consensus_final(counts, (int32_t*)c->kcount.p, (float*)c->rv.p, tv, tmean,
-                                           flags, (int32_t*)c->nsurv.p,
-                                           prune ? (int32_t*)c->nsurv.p + sh.n_pairs : nullptr, sh,
-                                           cfg->sample_frac, cfg->trim_lo, cfg->trim_hi,
-                                           (float*)c->sortbuf.p, results, st));
+        ERP_CK(erp::launch_consensus_final(cb, sh, cp, st));
     }
     if (c->opt[ERP_OPT_DEBUG_SNAP] && phase == 0 && c->snap_bytes) {
         // + the consensus's rotation vectors (SoA [P][3][2 iters] f32) as they are at its end
@@ -897,14 +862,8 @@ std::vector<uint8_t> graph_key(const erp_ctx* c, const erp_pair_batch* b, float 
     key_put(k, ratio);
     key_put(k, c->matcher);
     key_put(k, c->opt);
-    const DevBuf* all[] = {&c->mblk, &c->zsel, &c->part, &c->part1, &c->pu, &c->ccount, &c->cand,
-                           &c->bsel, &c->edges, &c->gfin, &c->matches, &c->counts, &c->flags,
-                           &c->pts, &c->polyR, &c->polyQ, &c->idx, &c->gram, &c->hyps, &c->rv,
-                           &c->tv, &c->kcount, &c->tmean, &c->sortbuf, &c->w0, &c->results,
-                           &c->dscale, &c->lb, &c->ub, &c->surv, &c->nsurv, &c->wins, &c->rtab,
-                           &c->limbs, &c->tsplit, &c->ovf, &c->vchunk, &c->lipref, &c->inl,
-                           &c->hlite};
-    for (const DevBuf* d : all) key_put(k, d->p);
+    for (const CtxBuf& b : kCtxBufs)
+        if (b.graph) key_put(k, (c->*b.m).p);
     return k;
 }
 
@@ -1304,10 +1263,10 @@ erp_status erp_eight_point_estimation(erp_ctx* ctx, const double* h_bl, const do
 
 }  // extern "C"
 
-// debug (ERP_ALLOC_PAD): buffers whose canary bytes were overwritten, reported on stderr;
-// returns their number (0 without ERP_ALLOC_PAD)
 extern "C" int erp_debug_lip_counters(uint32_t* out64) { return erp::debug_lip_counters(out64); }
 
+// debug (after erp_debug_set_alloc_pad(N), N > 0): buffers whose canary bytes were overwritten,
+// reported on stderr; returns their number (0 when no pad is set)
 extern "C" int erp_debug_check_pads(void) {
     const size_t pad = alloc_pad();
     if (!pad) return 0;

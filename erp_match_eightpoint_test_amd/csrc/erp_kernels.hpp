@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/erp_match.h"
+#include "erp_consensus_ws.hpp"
 
 namespace erp {
 
@@ -35,25 +36,6 @@ struct Top2 {                     // partial k=2 result of one train chunk for o
     float d0;                     // best squared distance
     int32_t j0;                   // its train index (lowest index among ties)
     float d1;                     // second squared distance
-};
-
-// scratch the pipeline needs for one batch (all device pointers, sized by the context)
-struct Workspace {
-    Top2* part;                   // [pairs][max_nq] exact k=2 per query
-    erp_dmatch* matches;          // [pairs][max_nq]
-    int32_t* counts;              // [pairs] M
-    double* pts;                  // [pairs][max_nq + 1][6] bearings (l, r); last row = 0
-    uint32_t* polyR;              // [pairs][65][31]  x^(l(M-1)) mod P
-    uint32_t* polyQ;              // [pairs][kMaxQ][31]
-    uint32_t* sel;                // [pairs][waves][sel_words][64] sample selection bitmaps
-    double* gram;                 // [pairs][iters][36]
-    erp_hypothesis* hyps;         // [pairs][iters]
-    float* rv;                    // [pairs][3][2*iters] valid R (SoA)
-    float* tv;                    // [pairs][2*iters][3] their T
-    int32_t* kcount;              // [pairs]
-    double* tmean;                // [pairs][2*iters]
-    float* sortbuf;               // [pairs][2*iters] exact tie resolution scratch
-    int32_t* flags;               // [pairs] internal error flags
 };
 
 struct BatchShape {
@@ -121,11 +103,8 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
                           const double* rtab, uint32_t* wins, uint32_t* selw, int32_t* flags,
                           hipStream_t st, int part);
 // rtab[d] = 1/d rounded up, d < kRecipTable (the sampler's exact modulo); *bad counts entries
-// whose one-sided error bound fails (never, by construction; checked once per context)
-constexpr int kRecipTable = 65538;
-// the sampler's table allocation: rtab [kRecipTable] doubles, then the magic-number table
-// [kRecipTable] uint64 (ERP_SAMPLER_MAGIC), then the check counter
-constexpr size_t kRecipTableBytes = (size_t)kRecipTable * 16 + 8;
+// whose one-sided error bound fails (never, by construction; checked once per context).  The
+// table allocation (reciprocals, magic numbers, check counter): ConsensusLayout::rtab
 // host: mtab[d] = m_d | (l_d - 1) << 32 (kernels.hip mod_magic_i24); false if a divisor fails
 // the exact Granlund-Montgomery condition (never, by construction)
 bool build_magic_table(uint64_t* mtab, int n);
@@ -156,13 +135,8 @@ hipError_t launch_eigen(const int32_t* counts, const double* gram, const BatchSh
                         hipStream_t st, int fused = 0, bool want_e = true,
                         float* hl = nullptr, int32_t* wsum = nullptr);
 // (hl != NULL, round 5: the estimates go to the lite layout -- hl[p][9][iters] f32 R1, R2, T,
-// an invalid rotation's x NaN, plus per-64-iteration-wave counts / bounding boxes wsum -- in
-// hyp_lite_bytes(sh) (hl, then wsum), for launch_valid_place instead of records)
-size_t hyp_lite_bytes(const BatchShape& sh);
-hipError_t launch_valid_place(const int32_t* counts, const float* hl, const int32_t* wsum,
-                              const BatchShape& sh, double sample_frac, float* rv, float* tv,
-                              int32_t* kcount, float* rv_aos, float* dscale, float* edges,
-                              hipStream_t st);
+// an invalid rotation's x NaN, plus per-64-iteration-wave counts / bounding boxes wsum -- the
+// two parts of ConsensusLayout::hlite, for launch_valid_place instead of records)
 // (want_e = false: estimate_kernel leaves the records' E unwritten -- the batch pipeline when the
 // caller did not ask for the hypothesis records; nothing downstream reads E)
 // the opt-in inlier count (cfg.inlier_thr > 0): every iteration's matches with
@@ -183,41 +157,56 @@ hipError_t launch_gram_all(const double* pts, int32_t m, double* gram, hipStream
 hipError_t launch_consensus_input(const float* rvec, const float* tvec, int K, int stride, float* rv,
                                   float* tv, int32_t* kcount, float* dscale, int32_t* flags,
                                   hipStream_t st);
+
+// The consensus stage's device pointers: the context's scratch buffers by their base (what is
+// where inside them is erp_consensus_ws.hpp's business, turned into typed pointers by
+// kernels.hip consensus_views) and the call's inputs / outputs.
+struct ConsensusBufs {
+    const int32_t* counts;        // [P] M (null when the valid list was given directly)
+    const int32_t* flags;         // [P] internal error flags
+    int32_t* kcount;              // [P] K
+    float* rv;                    // [P][3][2 iters] valid R (SoA)
+    float* tv;                    // [P][2 iters][3] their T (the context's or the caller's)
+    float* rv_aos;                // optional output R_vec_arr (may be null)
+    float* dscale;                // [P] bounding-box scale
+    double* tmean;                // [P][2 iters] (the context's or the caller's)
+    double* lb;                   // lb / ub / bsel: the context's, or the caller's own for the
+    double* ub;                   // row-sharded entry points
+    int32_t* bsel;
+    void *zsel, *surv, *nsurv, *edges, *lipref, *sortbuf, *hlite;  // ConsensusLayout's buffers
+    erp_pair_result* results;
+};
+struct ConsensusParams {
+    double sample_frac, trim_lo, trim_hi;
+    int shard, nshards;           // the row shard of the bounds pass (0, 1: every row)
+    bool prune;                   // false = the small-batch route: every row binned, no lists
+    int lip2, lipg, flat_pct, hint;  // the pruning route (capi.hip pruning_opts)
+    bool edges_ready;             // launch_valid_place wrote the first-pass edges already
+};
+hipError_t launch_valid_place(const ConsensusBufs& b, const BatchShape& sh,
+                              const ConsensusParams& cp, hipStream_t st);
 // per-row [LB, UB] of the trimmed mean and the bins holding ranks lo / hi-1 (bsel[row][2])
-size_t consensus_edges_bytes(int n_pairs);
-hipError_t launch_consensus_zoom(const int32_t* kcount, const float* rv, const float* dscale,
-                                 float* edges, const BatchShape& sh, double trim_lo,
-                                 double trim_hi, double* lb, double* ub, const int32_t* bsel,
-                                 const int32_t* surv, int32_t* nsurv, int32_t* zsel, int level,
-                                 hipStream_t st);
-hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const float* dscale,
-                                   float* edges, const BatchShape& sh, double trim_lo,
-                                   double trim_hi, double* lb, double* ub, int32_t* bsel,
-                                   int shard, int nshards, int32_t* rlist, int32_t* rcount,
-                                   int32_t* zsel, int lip2, int32_t* list2, void* lipref,
-                                   int lipg, int flat_pct, int use_hint, hipStream_t st,
-                                   bool edges_ready = false);
-size_t lipref_bytes(int n_pairs, int stride);
+hipError_t launch_consensus_bounds(const ConsensusBufs& b, const BatchShape& sh,
+                                   const ConsensusParams& cp, hipStream_t st);
+hipError_t launch_consensus_zoom(const ConsensusBufs& b, const BatchShape& sh,
+                                 const ConsensusParams& cp, int level, hipStream_t st);
 // survivors = rows with LB <= min UB (again = 1: only pairs the refine pass touched)
-hipError_t launch_consensus_select(const int32_t* kcount, const double* lb, const double* ub,
-                                   const BatchShape& sh, double trim_lo, double trim_hi,
-                                   int32_t* surv, int32_t* nsurv, double* tmean, int again,
-                                   hipStream_t st);
+hipError_t launch_consensus_select(const ConsensusBufs& b, const BatchShape& sh,
+                                   const ConsensusParams& cp, int again, hipStream_t st);
 // tighter [LB, UB] for the current survivors (exact inner sums + sub-bins of the boundary bins)
-hipError_t launch_consensus_refine(const int32_t* kcount, const float* rv, const float* dscale,
-                                   const BatchShape& sh, double trim_lo, double trim_hi,
-                                   const int32_t* surv, const int32_t* nsurv, const int32_t* bsel,
-                                   double* lb, double* ub, int32_t* list2, void* lipref,
-                                   int use_hint, hipStream_t st);
-hipError_t launch_consensus_rows(const int32_t* kcount, const float* rv, const float* dscale,
-                                 const BatchShape& sh, double trim_lo, double trim_hi,
-                                 const int32_t* surv, const int32_t* nsurv, const int32_t* bsel,
-                                 double* tmean, hipStream_t st);
-hipError_t launch_consensus_final(const int32_t* counts, const int32_t* kcount, const float* rv,
-                                  const float* tv, const double* tmean, const int32_t* flags,
-                                  const int32_t* nsurv, const int32_t* nbin, const BatchShape& sh,
-                                  double sample_frac, double trim_lo, double trim_hi,
-                                  float* sortbuf, erp_pair_result* results, hipStream_t st);
-int sortbuf_len(int iters);        // power of two >= 2*iters (exact tie re-scoring scratch)
+hipError_t launch_consensus_refine(const ConsensusBufs& b, const BatchShape& sh,
+                                   const ConsensusParams& cp, hipStream_t st);
+hipError_t launch_consensus_rows(const ConsensusBufs& b, const BatchShape& sh,
+                                 const ConsensusParams& cp, hipStream_t st);
+hipError_t launch_consensus_final(const ConsensusBufs& b, const BatchShape& sh,
+                                  const ConsensusParams& cp, hipStream_t st);
+// after row-sharded bounds (not combined over the shards): binned rows = -1 for every pair
+hipError_t consensus_mark_unbinned(const ConsensusBufs& b, const BatchShape& sh, hipStream_t st);
+// debug snapshot right after the bounds pass: lb, ub [P][2 iters] f64, the first-stage list
+// counts [P] i32 (-1 without pruning), then the first-stage references (float4 [P][cap]), their
+// U [P] f64 and counts [P] i32; dst = device memory of consensus_snapshot_bytes(sh)
+size_t consensus_snapshot_bytes(const BatchShape& sh);
+hipError_t consensus_snapshot(const ConsensusBufs& b, const BatchShape& sh,
+                              const ConsensusParams& cp, void* dst, hipStream_t st);
 
 }  // namespace erp

@@ -2238,11 +2238,7 @@ __global__ __launch_bounds__(1024) void consensus_input_kernel(const float* __re
 // blocks (39 KB of histograms each) per CU.  The d-space bin edges are per pair
 // (consensus_edges_kernel); the epilogue holds its slice's edges in registers.
 constexpr int kBoundRows = 16;       // rows per bounds block
-constexpr int kBinShift = 19;         // bin = key >> 19: 16 bins per binade of s = d^2
-constexpr int kMantBits = 23 - kBinShift;
-constexpr int kBinsPerBinade = 1 << kMantBits;  // (= 32 per binade of the distance)
-constexpr int kBinades = 36;          // of s (576 bins: 4 blocks of 39 KB per CU)
-constexpr int kNB = kBinsPerBinade * kBinades;  // 576
+// (kBinShift, kMantBits, kBinsPerBinade, kBinades, kNB: erp_consensus_ws.hpp)
 constexpr int kSubBits = 10;          // 1024 sub-bins per bin (refine / exact pass) ...
 constexpr int kNS = 1 << kSubBits;
 constexpr int kLowBits = kBinShift - kSubBits;  // ... and below them the exact values
@@ -2652,10 +2648,7 @@ constexpr int kLipMinK = 1024;  // smaller sets: no pre-pruning (every non-refer
 #endif
 constexpr float kLipGFac = ERP_LIP_GFAC;
 constexpr int kGradBlocks = 2048;  // consensus_grad_kernel's grid (grid-stride over the references)
-#ifndef ERP_LIP2_STEP
-#define ERP_LIP2_STEP 4
-#endif
-constexpr int kLip2Step = ERP_LIP2_STEP;  // 1 in 4 L1 rows is a second-stage reference
+// (kLip2Step, ERP_LIP2_STEP: erp_consensus_ws.hpp)
 static_assert((kLip2Step & (kLip2Step - 1)) == 0, "power of two (is_ref2)");
 
 // The references of a pruning pass, staged ONCE per pair (consensus_lip_refs_kernel) into
@@ -2679,7 +2672,6 @@ constexpr int kLipChunk2 = 512;  // references per LDS chunk
 #endif
 constexpr double kLipM = ERP_LIP_MARGIN;
 constexpr double kLipPrunedLB = 1.0 + 0.5 * kLipM;
-int lipref_cap(int stride) { return stride / kLip2Step + 64; }  // >= refs of any mode
 
 // one block per pair.  Modes: stage 1 (slist == nullptr, zb == nullptr): rows ra + c lstep of
 // the shard (pairs with K >= kLipMinK); list mode (slist, zb == nullptr): survivor-list
@@ -3093,13 +3085,14 @@ __device__ __forceinline__ void for_columns(const float* __restrict__ X, const f
 // bound width ~2e-5, ~1 700 survivors per pair into the exact pass); on the interval they are
 // bracketed at 2^2-2^3 keys.  The window placement is only a heuristic: a rank that falls
 // outside its window fails the `ok` test below and the row keeps its old bounds.
-constexpr int kHintCands = 4;
-constexpr int kHintManyRows = 256;
+constexpr int kHintManyRows = 256;  // (kHintCands: erp_consensus_ws.hpp)
 struct HintCand {
     double T;
     int32_t row;  // -1: none
     uint32_t va, vb, pad;
 };
+static_assert(sizeof(HintCand) == kHintCandBytes && sizeof(float4) == kFloat4Bytes,
+              "erp_consensus_ws.hpp lays these out by size");
 struct RefineWin {
     uint32_t a0, a1, b0, b1;  // key windows [a0, a1) (rank lo), [b0, b1) (rank hi-1)
     int wa, wb;               // sub-bin k of a window covers keys [x0 + (k << w), + 2^w)
@@ -4882,19 +4875,81 @@ hipError_t launch_eigen(const int32_t* counts, const double* gram, const BatchSh
     return hipGetLastError();
 }
 
-size_t hyp_lite_bytes(const BatchShape& sh) {
-    const size_t P = sh.n_pairs, nw = (sh.iters + 63) / 64;
-    return P * 9 * sh.iters * sizeof(float) + P * nw * 8 * sizeof(int32_t);
+// The typed pointers into the consensus scratch (b's buffers cut up by erp_consensus_ws.hpp's
+// layout): the only place that does arithmetic on a scratch pointer.
+struct LipRefViews {
+    float4* ref;
+    double* U;
+    int32_t* cnt;
+    int32_t* r2cnt;
+    int32_t* r2list;
+    int cap;
+    float4* gref;
+    int32_t* gsel;
+    int32_t* gcnt;
+    int32_t* goff;
+    int gcap;
+    int32_t* nflat;
+    HintCand* hcand;
+};
+struct ConsensusViews {
+    int stride;                       // rows per pair = 2 * iters
+    int32_t *surv, *zsel;             // whole buffers
+    int32_t *nsurv, *nbin, *uoff, *n2, *nfb;  // the counts block
+    float *edges, *edz;               // first-pass and zoom edges
+    int32_t* zb;                      // zoom grids
+    LipRefViews lr;
+    float* score;                     // sortbuf as the tie re-scoring scratch, score_len per pair
+    int32_t* list2;                   // ... and as the row lists (free until consensus_final)
+    int score_len, l2_bounds_stride, l2_refine_stride;
+    const float* hl;                  // the lite estimates
+    const int32_t* wsum;
+};
+static ConsensusViews consensus_views(const ConsensusBufs& b, const BatchShape& sh) {
+    const ConsensusLayout l = consensus_layout(sh.n_pairs, sh.iters);
+    ConsensusViews v;
+    v.stride = (int)l.stride;
+    v.surv = static_cast<int32_t*>(b.surv);
+    v.zsel = static_cast<int32_t*>(b.zsel);
+    v.nsurv = ws_at<int32_t>(b.nsurv, l.counts.nsurv);
+    v.nbin = ws_at<int32_t>(b.nsurv, l.counts.nbin);
+    v.uoff = ws_at<int32_t>(b.nsurv, l.counts.uoff);
+    v.n2 = ws_at<int32_t>(b.nsurv, l.counts.n2);
+    v.nfb = ws_at<int32_t>(b.nsurv, l.counts.nfb);
+    v.edges = ws_at<float>(b.edges, l.edges.first);
+    v.edz = ws_at<float>(b.edges, l.edges.zoom);
+    v.zb = ws_at<int32_t>(b.edges, l.edges.zgrid);
+    const auto& r = l.lipref;
+    v.lr.ref = ws_at<float4>(b.lipref, r.ref);
+    v.lr.U = ws_at<double>(b.lipref, r.U);
+    v.lr.cnt = ws_at<int32_t>(b.lipref, r.cnt);
+    v.lr.r2cnt = ws_at<int32_t>(b.lipref, r.r2cnt);
+    v.lr.r2list = ws_at<int32_t>(b.lipref, r.r2list);
+    v.lr.cap = (int)r.cap;
+    v.lr.gref = ws_at<float4>(b.lipref, r.gref);
+    v.lr.gsel = ws_at<int32_t>(b.lipref, r.gsel);
+    v.lr.gcnt = ws_at<int32_t>(b.lipref, r.gcnt);
+    v.lr.goff = ws_at<int32_t>(b.lipref, r.goff);
+    v.lr.gcap = (int)r.gcap;
+    v.lr.nflat = ws_at<int32_t>(b.lipref, r.nflat);
+    v.lr.hcand = ws_at<HintCand>(b.lipref, r.hcand);
+    v.score = ws_at<float>(b.sortbuf, l.sortbuf.score);
+    v.list2 = ws_at<int32_t>(b.sortbuf, l.sortbuf.list2);
+    v.score_len = (int)l.sortbuf.len;
+    v.l2_bounds_stride = (int)l.sortbuf.list2_bounds_stride;
+    v.l2_refine_stride = (int)l.sortbuf.list2_refine_stride;
+    v.hl = ws_at<float>(b.hlite, l.hlite.hl);
+    v.wsum = ws_at<int32_t>(b.hlite, l.hlite.wsum);
+    return v;
 }
 
-hipError_t launch_valid_place(const int32_t* counts, const float* hl, const int32_t* wsum,
-                              const BatchShape& sh, double sample_frac, float* rv, float* tv,
-                              int32_t* kcount, float* rv_aos, float* dscale, float* edges,
-                              hipStream_t st) {
+hipError_t launch_valid_place(const ConsensusBufs& b, const BatchShape& sh,
+                              const ConsensusParams& cp, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
     dim3 grid((sh.iters + 1023) / 1024, sh.n_pairs);
-    ERP_LAUNCH(valid_place_kernel, grid, dim3(1024), 0, st, counts, hl, sh.iters,
-                       sample_frac, wsum, (sh.iters + 63) / 64, rv, tv, kcount, rv_aos, dscale,
-                       edges);
+    ERP_LAUNCH(valid_place_kernel, grid, dim3(1024), 0, st, b.counts, v.hl, sh.iters,
+                       cp.sample_frac, v.wsum, (sh.iters + 63) / 64, b.rv, b.tv, b.kcount,
+                       b.rv_aos, b.dscale, v.edges);
     return hipGetLastError();
 }
 
@@ -4950,20 +5005,18 @@ hipError_t launch_consensus_input(const float* rvec, const float* tvec, int K, i
     return hipGetLastError();
 }
 
-// [P][2][kNB] first-pass edges, [P][2][kNB] zoom edges, [P] zoom grids
-size_t consensus_edges_bytes(int n_pairs) {
-    return (size_t)n_pairs * 4 * kNB * sizeof(float) + (size_t)n_pairs * sizeof(int32_t);
-}
-
-hipError_t launch_consensus_zoom(const int32_t* kcount, const float* rv, const float* dscale,
-                                 float* edges, const BatchShape& sh, double trim_lo,
-                                 double trim_hi, double* lb, double* ub, const int32_t* bsel,
-                                 const int32_t* surv, int32_t* nsurv, int32_t* zsel, int level,
-                                 hipStream_t st) {
-    const int P = sh.n_pairs, stride = 2 * sh.iters;
-    float* edz = edges + (size_t)P * 2 * kNB;
-    int32_t* zb = reinterpret_cast<int32_t*>(edges + (size_t)P * 4 * kNB);
-    int32_t* uoff = nsurv + 2 * P;  // free until the refine pass (launch_consensus_refine)
+hipError_t launch_consensus_zoom(const ConsensusBufs& b, const BatchShape& sh,
+                                 const ConsensusParams& cp, int level, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
+    const int P = sh.n_pairs, stride = v.stride;
+    const int32_t* kcount = b.kcount;
+    const float *rv = b.rv, *dscale = b.dscale;
+    const double trim_lo = cp.trim_lo, trim_hi = cp.trim_hi;
+    double *lb = b.lb, *ub = b.ub;
+    const int32_t *bsel = b.bsel, *surv = v.surv;
+    int32_t *nsurv = v.nsurv, *zsel = v.zsel, *zb = v.zb;
+    float* edz = v.edz;
+    int32_t* uoff = v.uoff;  // free until the refine pass (launch_consensus_refine)
     if (level == 1)
         ERP_LAUNCH((consensus_zoom_prep_kernel<6, kMantBits>), dim3(P), dim3(256), 0, st,
                            kcount, dscale, surv, (const int32_t*)nsurv, bsel, 1, stride, trim_lo,
@@ -4988,72 +5041,23 @@ hipError_t launch_consensus_zoom(const int32_t* kcount, const float* rv, const f
     return hipGetLastError();
 }
 
-// the pruning references' scratch: [P][cap] float4, lU [P] doubles, lcnt [P] ints, then the
-// second-stage reference list [P][stride] ints and its counts [P]
-// then the gradient references: gref [P][gcap][2] float4, gsel [P][gcap], gcnt [P], goff [P + 1]
-// (>= the stage-1 references; the second stage's -- a quarter of L1 -- are capped at it)
-// then the flat gate [P] ints (consensus_flat_gate_kernel) and the refine pass's rank-key hint
-// candidates [P][kHintCands] (consensus_hint_kernel)
-static int grad_cap(int stride) { return stride / 4 + 64; }
-size_t lipref_bytes(int n_pairs, int stride) {
-    const size_t gcap = grad_cap(stride);
-    return (size_t)n_pairs * lipref_cap(stride) * sizeof(float4) + (size_t)n_pairs * 16 +
-           (size_t)n_pairs * stride * 4 + 64 + (size_t)n_pairs * gcap * 2 * sizeof(float4) +
-           (size_t)n_pairs * gcap * 4 + (size_t)n_pairs * 8 + 128 +
-           (size_t)n_pairs * 4 + 16 + (size_t)n_pairs * kHintCands * sizeof(HintCand);
-}
-struct LipRefViews {
-    float4* ref;
-    double* U;
-    int32_t* cnt;
-    int32_t* r2cnt;
-    int32_t* r2list;
-    int cap;
-    float4* gref;
-    int32_t* gsel;
-    int32_t* gcnt;
-    int32_t* goff;
-    int gcap;
-    int32_t* nflat;
-    HintCand* hcand;
-};
-static LipRefViews lipref_views(void* base, int n_pairs, int stride) {
-    LipRefViews v;
-    v.cap = lipref_cap(stride);
-    v.ref = reinterpret_cast<float4*>(base);
-    v.U = reinterpret_cast<double*>(v.ref + (size_t)n_pairs * v.cap);
-    v.cnt = reinterpret_cast<int32_t*>(v.U + n_pairs);
-    v.r2cnt = v.cnt + n_pairs;
-    v.r2list = v.r2cnt + n_pairs;
-    v.gcap = grad_cap(stride);
-    uintptr_t gb = reinterpret_cast<uintptr_t>(v.r2list + (size_t)n_pairs * stride) + 64;
-    gb = (gb + 15) & ~(uintptr_t)15;
-    v.gref = reinterpret_cast<float4*>(gb);
-    v.gsel = reinterpret_cast<int32_t*>(v.gref + (size_t)n_pairs * v.gcap * 2);
-    v.gcnt = v.gsel + (size_t)n_pairs * v.gcap;
-    v.goff = v.gcnt + n_pairs;
-    v.nflat = v.goff + n_pairs + 1;
-    uintptr_t cb = reinterpret_cast<uintptr_t>(v.nflat + n_pairs);
-    v.hcand = reinterpret_cast<HintCand*>((cb + 15) & ~(uintptr_t)15);
-    return v;
-}
-
-hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const float* dscale,
-                                   float* edges, const BatchShape& sh, double trim_lo,
-                                   double trim_hi, double* lb, double* ub, int32_t* bsel,
-                                   int shard, int nshards, int32_t* rlist, int32_t* rcount,
-                                   int32_t* zsel, int lip2, int32_t* list2, void* lipref,
-                                   int lipg, int flat_pct, int use_hint, hipStream_t st,
-                                   bool edges_ready) {
+hipError_t launch_consensus_bounds(const ConsensusBufs& b, const BatchShape& sh,
+                                   const ConsensusParams& cp, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
+    const int32_t* kcount = b.kcount;
+    const float *rv = b.rv, *dscale = b.dscale;
+    float* edges = v.edges;
+    const double trim_lo = cp.trim_lo, trim_hi = cp.trim_hi;
+    double *lb = b.lb, *ub = b.ub;
+    int32_t *bsel = b.bsel, *zsel = v.zsel;
+    const int shard = cp.shard, nshards = cp.nshards, lipg = cp.lipg, flat_pct = cp.flat_pct;
+    // the first stage's row list and its counts (the binned-row counts the final stage reports)
+    int32_t *rlist = v.surv, *rcount = v.nbin;
     const float gfac = kLipGFac;
-    if (!edges_ready)
+    if (!cp.edges_ready)
         ERP_LAUNCH(consensus_edges_kernel, dim3(sh.n_pairs), dim3(256), 0, st, dscale, edges);
-    const int stride = 2 * sh.iters;
-    if (!rlist) {  // every row of the shard (rcount = -1: no pre-pruning)
-        if (rcount) {
-            const hipError_t me = hipMemsetAsync(rcount, 0xFF, sizeof(int32_t) * sh.n_pairs, st);
-            if (me != hipSuccess) return me;
-        }
+    const int stride = v.stride;
+    if (!cp.prune) {  // every row of the shard, no pre-pruning (and no binned-row counts)
         const int rows = (stride + nshards - 1) / nshards + 1;  // >= any shard's rows
         dim3 grid((rows + kBoundRows - 1) / kBoundRows, sh.n_pairs);
         ERP_LAUNCH(consensus_bounds_kernel, grid, dim3(256), 0, st, kcount, rv, dscale,
@@ -5068,8 +5072,8 @@ hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const
     ERP_LAUNCH(consensus_bounds_kernel, g1, dim3(256), 0, st, kcount, rv, dscale, edges,
                        stride, trim_lo, trim_hi, lb, ub, bsel, shard, nshards, kLipStep);
     const int P = sh.n_pairs;
-    const LipRefViews lr = lipref_views(lipref, P, stride);
-    const bool two = lip2 && list2;  // second pre-pruning stage
+    const LipRefViews& lr = v.lr;
+    const bool two = cp.lip2;  // second pre-pruning stage
     // (the list counters rcount and r2cnt are reset by the references kernel)
     ERP_LAUNCH(consensus_lip_refs_kernel, dim3(P), dim3(256), 0, st, kcount, rv, stride,
                        trim_lo, trim_hi, (const double*)lb, (const double*)ub,
@@ -5097,14 +5101,14 @@ hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const
                        lr.cap, two ? lr.r2list : nullptr, two ? lr.r2cnt : nullptr,
                        (lipg & 1) ? (const float4*)lr.gref : nullptr, (const int32_t*)lr.gcnt,
                        lr.gcap);
-    int32_t* uoff = rcount + P;  // [n_pairs + 1] after the counts
+    int32_t* uoff = v.uoff;
     if (flat_pct > 0 && nshards == 1) {
         // flat pairs: refine the first-stage references, then re-run the first stage
         ERP_LAUNCH(consensus_flat_gate_kernel, dim3((P + 255) / 256), dim3(256), 0, st,
                            kcount, rcount, two ? lr.r2cnt : nullptr, P, flat_pct, trim_lo,
                            trim_hi, lr.nflat);
         const HintCand* hint = nullptr;
-        if (use_hint) {
+        if (cp.hint) {
             ERP_LAUNCH(consensus_hint_kernel, dim3(P, kHintCands), dim3(256), 0, st,
                                kcount, rv, stride, trim_lo, trim_hi, (const int32_t*)nullptr,
                                (const int32_t*)lr.nflat, kLipStep, 0, (const double*)ub, lr.hcand);
@@ -5136,9 +5140,9 @@ hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const
         // second stage: the L1 rows with is_ref2 (listed apart by the first stage) on the fine
         // grid, the other L1 rows tested against them; the survivors (list2, counts after the
         // unit prefix) get the coarse pass
-        float* edz = edges + (size_t)P * 2 * kNB;
-        int32_t* zb = reinterpret_cast<int32_t*>(edges + (size_t)P * 4 * kNB);
-        int32_t* n2 = uoff + P + 1;
+        float* edz = v.edz;
+        int32_t *zb = v.zb, *n2 = v.n2, *nfb = v.nfb;
+        int32_t* list2 = v.list2;  // (rows per pair here: v.l2_bounds_stride = stride)
         ERP_LAUNCH(consensus_ref2_prep_kernel, dim3(P), dim3(256), 0, st, kcount, dscale,
                            (const double*)ub, (const int32_t*)bsel, (const int32_t*)rcount, stride,
                            trim_lo, trim_hi, shard, nshards, zb, edz);
@@ -5149,12 +5153,12 @@ hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const
                            (const float*)edz, (const int32_t*)zb, stride, trim_lo, trim_hi, lb, ub,
                            (const int32_t*)lr.r2list, (const int32_t*)lr.r2cnt,
                            (const int32_t*)uoff, P, zsel, 1, dscale, bsel);
-        // (n2 and nfb = n2 + P reset by the references kernel)
+        // (n2 and nfb reset by the references kernel)
         ERP_LAUNCH(consensus_lip_refs_kernel, dim3(P), dim3(256), 0, st, kcount, rv,
                            stride, trim_lo, trim_hi, (const double*)lb, (const double*)ub,
                            (const int32_t*)lr.r2list, (const int32_t*)lr.r2cnt, 1, shard,
                            nshards, (const int32_t*)zb, lr.ref, lr.U, lr.cnt, lr.cap,
-                           (const int32_t*)nullptr, n2, n2 + P);
+                           (const int32_t*)nullptr, n2, nfb);
         if (lipg & 2) {  // G of the central second-stage references (fine bounds)
             ERP_LAUNCH(consensus_grad_select_kernel, dim3(P), dim3(256), 0, st, kcount,
                                stride, (const double*)lb, (const double*)ub, (const int32_t*)bsel,
@@ -5170,13 +5174,13 @@ hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const
         ERP_LAUNCH(consensus_lipschitz2_kernel, dim3((srows + 511) / 512, P), dim3(256), 0,
                            st, kcount, rv, stride, lb, ub, (const int32_t*)rlist,
                            (const int32_t*)rcount, (const int32_t*)zb, (const int32_t*)bsel, list2,
-                           n2, n2 + P, (const float4*)lr.ref, (const double*)lr.U,
+                           n2, nfb, (const float4*)lr.ref, (const double*)lr.U,
                            (const int32_t*)lr.cnt, lr.cap,
                            (lipg & 2) ? (const float4*)lr.gref : nullptr, (const int32_t*)lr.gcnt,
                            lr.gcap);
         ERP_LAUNCH(consensus_ref2_count_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P,
                            (const int32_t*)zb, (const int32_t*)lr.r2cnt, (const int32_t*)n2,
-                           (const int32_t*)(n2 + P), rcount);
+                           (const int32_t*)nfb, rcount);
         blist = list2;
         bcount = n2;
     }
@@ -5191,29 +5195,29 @@ hipError_t launch_consensus_bounds(const int32_t* kcount, const float* rv, const
     return hipGetLastError();
 }
 
-hipError_t launch_consensus_select(const int32_t* kcount, const double* lb, const double* ub,
-                                   const BatchShape& sh, double trim_lo, double trim_hi,
-                                   int32_t* surv, int32_t* nsurv, double* tmean, int again,
-                                   hipStream_t st) {
-    ERP_LAUNCH(consensus_select_kernel, dim3(sh.n_pairs), dim3(1024), 0, st, kcount, lb, ub,
-                       2 * sh.iters, trim_lo, trim_hi, surv, nsurv, tmean, again);
+hipError_t launch_consensus_select(const ConsensusBufs& b, const BatchShape& sh,
+                                   const ConsensusParams& cp, int again, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
+    ERP_LAUNCH(consensus_select_kernel, dim3(sh.n_pairs), dim3(1024), 0, st, b.kcount,
+                       (const double*)b.lb, (const double*)b.ub, v.stride, cp.trim_lo, cp.trim_hi,
+                       v.surv, v.nsurv, b.tmean, again);
     return hipGetLastError();
 }
 
-hipError_t launch_consensus_refine(const int32_t* kcount, const float* rv, const float* dscale,
-                                   const BatchShape& sh, double trim_lo, double trim_hi,
-                                   const int32_t* surv, const int32_t* nsurv, const int32_t* bsel,
-                                   double* lb, double* ub, int32_t* list2, void* lipref,
-                                   int use_hint, hipStream_t st) {
-    // scratch after nsurv[n_pairs] and the bounds-list counts[n_pairs]: the unit prefix
-    // [n_pairs + 1], then the counts of list2 [n_pairs]
-    const int P = sh.n_pairs, stride = 2 * sh.iters, l2stride = sortbuf_len(sh.iters);
-    int32_t* uoff = const_cast<int32_t*>(nsurv) + 2 * P;
-    int32_t* n2 = uoff + P + 1;
-    const LipRefViews lr = lipref_views(lipref, P, stride);
-    // (0) the rank-key hint of pairs with > kRefineMin survivors (use_hint = 0: none)
+hipError_t launch_consensus_refine(const ConsensusBufs& b, const BatchShape& sh,
+                                   const ConsensusParams& cp, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
+    const int P = sh.n_pairs, stride = v.stride, l2stride = v.l2_refine_stride;
+    const int32_t* kcount = b.kcount;
+    const float *rv = b.rv, *dscale = b.dscale;
+    const double trim_lo = cp.trim_lo, trim_hi = cp.trim_hi;
+    double *lb = b.lb, *ub = b.ub;
+    const int32_t *surv = v.surv, *nsurv = v.nsurv, *bsel = b.bsel;
+    int32_t *uoff = v.uoff, *n2 = v.n2, *list2 = v.list2;
+    const LipRefViews& lr = v.lr;
+    // (0) the rank-key hint of pairs with > kRefineMin survivors (cp.hint = 0: none)
     const HintCand* hint = nullptr;
-    if (use_hint) {
+    if (cp.hint) {
         // (pairs with <= kHintManyRows survivors -- a one-cluster pair after the zoom has ~20 --
         // keep the default windows: the hint's K-column passes would cost more than they save)
         ERP_LAUNCH(consensus_hint_kernel, dim3(P, kHintCands), dim3(256), 0, st, kcount,
@@ -5247,37 +5251,60 @@ hipError_t launch_consensus_refine(const int32_t* kcount, const float* rv, const
     return hipGetLastError();
 }
 
-hipError_t launch_consensus_rows(const int32_t* kcount, const float* rv, const float* dscale,
-                                 const BatchShape& sh, double trim_lo, double trim_hi,
-                                 const int32_t* surv, const int32_t* nsurv, const int32_t* bsel,
-                                 double* tmean, hipStream_t st) {
-    int32_t* uoff = const_cast<int32_t*>(nsurv) + 2 * sh.n_pairs;  // as in launch_consensus_refine
+hipError_t launch_consensus_rows(const ConsensusBufs& b, const BatchShape& sh,
+                                 const ConsensusParams& cp, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
+    const int32_t* uoff = v.uoff;
     if (sh.n_pairs <= 16)
         uoff = nullptr;  // (consensus_rows_kernel walks the counts itself: one launch fewer)
     else
-        ERP_LAUNCH(list_prefix_kernel, dim3(1), dim3(1024), 0, st, nsurv, sh.n_pairs, 1, 0,
-                           uoff);
-    ERP_LAUNCH(consensus_rows_kernel, dim3(2048), dim3(256), 0, st, kcount, rv, dscale,
-                       2 * sh.iters, trim_lo, trim_hi, surv, nsurv, bsel, tmean,
-                       (const int32_t*)uoff, sh.n_pairs);
+        ERP_LAUNCH(list_prefix_kernel, dim3(1), dim3(1024), 0, st, (const int32_t*)v.nsurv,
+                           sh.n_pairs, 1, 0, v.uoff);
+    ERP_LAUNCH(consensus_rows_kernel, dim3(2048), dim3(256), 0, st, (const int32_t*)b.kcount,
+                       (const float*)b.rv, (const float*)b.dscale, v.stride, cp.trim_lo,
+                       cp.trim_hi, (const int32_t*)v.surv, (const int32_t*)v.nsurv,
+                       (const int32_t*)b.bsel, b.tmean, uoff, sh.n_pairs);
     return hipGetLastError();
 }
 
-int sortbuf_len(int iters) {
-    int p = 1;
-    while (p < 2 * iters) p <<= 1;
-    return p;
+hipError_t launch_consensus_final(const ConsensusBufs& b, const BatchShape& sh,
+                                  const ConsensusParams& cp, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
+    ERP_LAUNCH(consensus_final_kernel, dim3(sh.n_pairs), dim3(1024), 0, st, b.counts,
+                       (const int32_t*)b.kcount, (const float*)b.rv, (const float*)b.tv,
+                       (const double*)b.tmean, b.flags, (const int32_t*)v.nsurv,
+                       cp.prune ? (const int32_t*)v.nbin : nullptr, v.stride, v.score_len,
+                       cp.sample_frac, cp.trim_lo, cp.trim_hi, v.score, b.results);
+    return hipGetLastError();
 }
 
-hipError_t launch_consensus_final(const int32_t* counts, const int32_t* kcount, const float* rv,
-                                  const float* tv, const double* tmean, const int32_t* flags,
-                                  const int32_t* nsurv, const int32_t* nbin, const BatchShape& sh,
-                                  double sample_frac, double trim_lo, double trim_hi,
-                                  float* sortbuf, erp_pair_result* results, hipStream_t st) {
-    ERP_LAUNCH(consensus_final_kernel, dim3(sh.n_pairs), dim3(1024), 0, st, counts, kcount,
-                       rv, tv, tmean, flags, nsurv, nbin, 2 * sh.iters, sortbuf_len(sh.iters), sample_frac,
-                       trim_lo, trim_hi, sortbuf, results);
-    return hipGetLastError();
+hipError_t consensus_mark_unbinned(const ConsensusBufs& b, const BatchShape& sh, hipStream_t st) {
+    const ConsensusViews v = consensus_views(b, sh);
+    return hipMemsetAsync(v.nbin, 0xFF, sizeof(int32_t) * sh.n_pairs, st);
+}
+
+size_t consensus_snapshot_bytes(const BatchShape& sh) {
+    const ConsensusLayout l = consensus_layout(sh.n_pairs, sh.iters);
+    return l.lb_bytes + l.ub_bytes + l.counts.nbin.count * 4 + l.lipref.snap_bytes;
+}
+
+hipError_t consensus_snapshot(const ConsensusBufs& b, const BatchShape& sh,
+                              const ConsensusParams& cp, void* dst, hipStream_t st) {
+    const ConsensusLayout l = consensus_layout(sh.n_pairs, sh.iters);
+    const ConsensusViews v = consensus_views(b, sh);
+    char* d = static_cast<char*>(dst);
+    const size_t nb = l.counts.nbin.count * 4;
+    hipError_t e = hipMemcpyAsync(d, b.lb, l.lb_bytes, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(d += l.lb_bytes, b.ub, l.ub_bytes, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return e;
+    if (cp.prune)
+        e = hipMemcpyAsync(d += l.ub_bytes, v.nbin, nb, hipMemcpyDeviceToDevice, st);
+    else  // (the small-batch route lists nothing: -1 = every row binned)
+        e = hipMemsetAsync(d += l.ub_bytes, 0xFF, nb, st);
+    if (e != hipSuccess) return e;
+    // + the first-stage references (float4 [P][cap]), their U [P] f64 and counts [P] i32
+    return hipMemcpyAsync(d + nb, v.lr.ref, l.lipref.snap_bytes, hipMemcpyDeviceToDevice, st);
 }
 
 }  // namespace erp

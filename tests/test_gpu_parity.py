@@ -326,14 +326,10 @@ def _batch(pairs, device="cuda"):
             int(np.diff(ol).max()), int(np.diff(orr).max()))
 
 
-def test_batch_pipeline_vs_oracle(ctx, oracle):
-    from erp_match_eightpoint_test_amd import PairBatchRunner, hyps_to_numpy, results_to_numpy
-    import torch
-    pairs = [synth.make_pair(1000 + i, n_kpts=n) for i, n in enumerate([512, 700, 300, 1024])]
-    args = _batch(pairs)
-    run = PairBatchRunner(ctx=ctx, iters=200)
-    outs = run.run(*args, want=("matches", "hyps", "samples", "rvec", "dist"))
-    torch.cuda.synchronize()
+def _check_batch_vs_oracle(oracle, pairs, outs, iters):
+    """outs = PairBatchRunner.run(..., want=("matches", "hyps", "samples", "rvec", "dist")) of
+    pairs, synchronised: every stage against the oracle"""
+    from erp_match_eightpoint_test_amd import hyps_to_numpy, results_to_numpy
     res = results_to_numpy(outs["results"])
     hyps = hyps_to_numpy(outs["hyps"])
     for i, p in enumerate(pairs):
@@ -344,7 +340,7 @@ def test_batch_pipeline_vs_oracle(ctx, oracle):
         assert np.array_equal(got.view(np.uint32).reshape(-1), ref.view(np.uint32).reshape(-1))
         kl = p["kp_l"][ref["queryIdx"]]
         kr = p["kp_r"][ref["trainIdx"]]
-        o = oracle.find(p["W"], p["H"], kl, kr, oracle.make_cfg(iters=200), detail=True)
+        o = oracle.find(p["W"], p["H"], kl, kr, oracle.make_cfg(iters=iters), detail=True)
         s = o["sample_n"]
         got_s = np.sort(outs["samples"][i, :, :s].cpu().numpy(), axis=1)
         assert np.array_equal(got_s, np.sort(o["samples"], axis=1))
@@ -361,6 +357,71 @@ def test_batch_pipeline_vs_oracle(ctx, oracle):
         live = np.isfinite(d)
         assert live.sum() >= 1 and np.all(dref[~live] >= dref.min())
         assert np.allclose(d[live], dref[live], rtol=1e-12, atol=0)
+    return res
+
+
+def test_batch_pipeline_vs_oracle(ctx, oracle):
+    from erp_match_eightpoint_test_amd import PairBatchRunner
+    import torch
+    pairs = [synth.make_pair(1000 + i, n_kpts=n) for i, n in enumerate([512, 700, 300, 1024])]
+    args = _batch(pairs)
+    run = PairBatchRunner(ctx=ctx, iters=200)
+    outs = run.run(*args, want=("matches", "hyps", "samples", "rvec", "dist"))
+    torch.cuda.synchronize()
+    _check_batch_vs_oracle(oracle, pairs, outs, 200)
+
+
+def _canary_child():
+    """body of test_consensus_scratch_canaries (a process of its own: the pad must be set before
+    the process's first allocation and never changed)"""
+    import oracle
+    import torch
+    from erp_match_eightpoint_test_amd import Context, PairBatchRunner, capi
+    oracle.build()
+    L = capi.load()
+    L.erp_debug_set_alloc_pad(256)
+    c = Context(0)
+    for name, v in (("small_batch", 0), ("lip2", 1), ("lipg", 3), ("flat_refs", 25),
+                    ("refine_hint", 1), ("zoom_levels", 2)):
+        c.set_option(name, v)
+    iters = 1100
+    sizes = [300, 310, 290, 305, 320, 295, 300, 315, 285]
+    pairs = [synth.make_pair(5200 + i, n_kpts=n) for i, n in enumerate(sizes)]
+    outs = PairBatchRunner(ctx=c, iters=iters).run(
+        *_batch(pairs), want=("matches", "hyps", "samples", "rvec", "dist"))
+    torch.cuda.synchronize()
+    # one single pair on the small-batch route (automatic: 1 pair x (2 iters)^2 <= 2e9)
+    c.set_option("small_batch", -1)
+    p = pairs[0]
+    mt, _, _, _ = oracle.match_two_image(p["desc_l"], p["desc_r"])
+    st, r, _ = _run_find_dev(c, p["kp_l"][mt["queryIdx"]], p["kp_r"][mt["trainIdx"]], p["W"],
+                             p["H"], iters)
+    assert L.erp_debug_check_pads() == 0
+    assert st == 0 and r["status"] == 0
+    res = _check_batch_vs_oracle(oracle, pairs, outs, iters)
+    assert np.all(res["status"] == 0)
+    assert res["K"].min() >= 1024  # every pair above the no-pre-pruning floor (kLipMinK)
+    # the single-pair route picks the batch's winner for that pair
+    assert r["K"] == res[0]["K"] and r["min_idx"] == res[0]["min_idx"]
+    assert np.abs(r["R"] - res[0]["R"]).max() <= TOL_RT
+    assert np.abs(r["T"] - res[0]["T"]).max() <= TOL_RT
+    print("canary child ok")
+
+
+def test_consensus_scratch_canaries(gpu_lib, oracle):
+    """every consensus route (second pre-pruning stage, gradient references of both stages, flat
+    route, refine hint, two zoom levels: both strides of the row lists in sortbuf) on 9 pairs
+    with 256 canary bytes behind every context buffer, then a single pair on the small-batch
+    route: no canary touched (erp_consensus_ws.hpp sizes every part the kernels write), all
+    statuses OK and the results equal to the oracle's as in test_batch_pipeline_vs_oracle"""
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path[:0] = [%r, %r]; import test_gpu_parity as t; t._canary_child()"
+            % (here, os.path.dirname(here)))
+    flags = ["-s"] if sys.flags.no_user_site else []
+    r = subprocess.run([sys.executable, *flags, "-c", code], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "canary child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 def test_batch_pipeline_hip_graph_replay(gpu_lib):
