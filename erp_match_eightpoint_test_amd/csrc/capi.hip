@@ -145,7 +145,8 @@ struct erp_ctx {
         -1,  // FLAT_REFS: pairs whose first stage kept > 25 % of the rows take the flat route
         1,   // BOUND_RATIO: the matcher's ratio test from the bf16 bounds where they suffice
         -1,  // DEBUG_STAGES: every stage group
-        0};  // DEBUG_SNAP
+        0,   // DEBUG_SNAP
+        -1}; // SAMPLER_TIERS: auto
     // debug (ERP_OPT_DEBUG_SNAP): lb, ub and the first-stage list counts right after the bounds
     // pass, fetched with erp_debug_snapshot
     DevBuf snap;
@@ -550,6 +551,7 @@ erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ra
     sh.sampler_lat = c->opt[ERP_OPT_SAMPLER_LAT];
     sh.sampler_split = c->opt[ERP_OPT_SAMPLER_SPLIT];
     sh.gram_tiles = c->opt[ERP_OPT_GRAM_TILES];
+    sh.sampler_tiers = c->opt[ERP_OPT_SAMPLER_TIERS];
     auto* counts = (int32_t*)c->counts.p;
     auto* flags = (int32_t*)c->flags.p;
     auto* hyps = (out && out->hyps) ? out->hyps : (erp_hypothesis*)c->hyps.p;
@@ -892,6 +894,7 @@ erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value) {
         case ERP_OPT_LIP2: lo = -1; hi = 1; break;
         case ERP_OPT_REFINE_HINT: lo = -1; hi = 1; break;
         case ERP_OPT_DEBUG_STAGES: lo = -1; hi = 63; break;
+        case ERP_OPT_SAMPLER_TIERS: lo = -1; hi = 4; break;
         default: break;
     }
     if (value < lo || value > hi) return ERP_INVALID_ARG;

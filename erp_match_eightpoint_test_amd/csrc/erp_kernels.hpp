@@ -48,8 +48,8 @@ struct BatchShape {
     int idx_stride;               // entries of one hypothesis in the debug samples output
     int sel_words;                // 31-step selection words per hypothesis (>= (M-1)/31 + 1)
     // route options (erp_ctx_set_option; -1 / 0 = automatic): the sampler's block kind and split
-    // replay, the Gram kernel's row tiles per wave
-    int sampler_lat = -1, sampler_split = -1, gram_tiles = 0;
+    // replay, the Gram kernel's row tiles per wave, the throughput sampler's launch tiers
+    int sampler_lat = -1, sampler_split = -1, gram_tiles = 0, sampler_tiers = -1;
 };
 
 hipError_t launch_set_i32(int32_t* p, int32_t v, hipStream_t st);  // (values via kernel args:

@@ -377,7 +377,10 @@ __device__ __forceinline__ int bm_index(int w, int lane) { return (w << (RS - 2)
 
 // replay blocks consume a step's LDS return `kReplayLag` steps after issuing it (fewer live
 // registers than consuming all 31 after the block: occupancy)
-constexpr int kReplayLag = 8;
+#ifndef ERP_REPLAY_LAG
+#define ERP_REPLAY_LAG 8  // (A/B builds: 1 .. 15, the lgkmcnt range)
+#endif
+constexpr int kReplayLag = ERP_REPLAY_LAG;
 
 // LDS masked OR with return: old = bm[a]; bm[a] = (old & ~mask) | data (one DS op: the bit
 // clear of the i >= s steps with data = 0, the "T[j] := T[i]" bit copy of the prefix steps).
@@ -394,8 +397,8 @@ __device__ __forceinline__ uint32_t lds_mskor_rtn(uint32_t addr, uint32_t mask, 
 // far): at most `lag` masked ORs may still be in flight after it (LDS returns in order; SMEM in
 // the count only makes the wait stricter)
 __device__ __forceinline__ void lds_wait_step(uint32_t& o, int v) {
-    if (min(30 - v, kReplayLag) >= 8)
-        asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(o) : : "memory");
+    if (30 - v >= kReplayLag)
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(o) : "n"(kReplayLag) : "memory");
     else
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(o) : : "memory");
 }
@@ -772,7 +775,9 @@ __device__ __forceinline__ uint32_t replay_block(uint32_t (&ring)[31], uint32_t*
 // One lane = one iteration; writes the iteration's selection bitmap in block space:
 // sel[p][w][b][lane] bit u <-> index i = M-1-31b-u (b = 0 .. (M-1)/31), exactly s bits set.
 // MODE 0: the throughput blocks on the position-major bitmap (nalloc = position words per half,
-// the allocation 2 * nalloc words); 2 / 3: the latency blocks, step by step / positions first,
+// the allocation 2 * nalloc words), for the pairs of this launch's tier only: s in (s_lo, s_hi],
+// s_hi + 32 <= nalloc (launch_sampler; every other workgroup leaves before it touches the LDS,
+// the mode register or memory); 2 / 3: the latency blocks, step by step / positions first,
 // on the lane-major bitmap (nalloc words per lane; constants prefetched one block ahead by vector
 // loads, two blocks per loop trip so that the two constant sets alternate without register
 // copies)
@@ -780,19 +785,20 @@ template <int MODE>
 __global__ __launch_bounds__(64) void sampler_kernel(
     const int32_t* __restrict__ counts, const uint32_t* __restrict__ wins, int nwaves, int nbw,
     double sample_frac, const double* __restrict__ rtab, uint32_t* __restrict__ selw,
-    int32_t* __restrict__ flags, int nalloc) {
+    int32_t* __restrict__ flags, int nalloc, int s_lo, int s_hi) {
     extern __shared__ uint32_t bm[];  // MODE 0: [2][nalloc]; else [nalloc][64]
     const int p = blockIdx.y, w = blockIdx.x, lane = wave_lane();
     const int M = counts[p];
     const int s = (int)(M * sample_frac);
     if (s < 1 || M < 2) return;
+    if (MODE == 0 && (s <= s_lo || s > s_hi)) return;  // another tier's pair
     // fp64 round-toward-zero for the rest of the wave (mod_rup_i24's fma; mod_rup stays exact
     // under it: trunc of a one-sided product, then an exact fma residual)
     // (inline asm: the compiler's mode-register pass would otherwise put the default mode back
     // in front of every fp64 instruction; nothing else in this kernel depends on fp64 rounding)
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 3\n\ts_nop 3" ::: "memory");
     // positions < s available, every other bitmap word of the allocation (nalloc words: the
-    // batch's largest s, rounded up to the allocation granule) clear
+    // tier's largest s + 32, rounded up to the allocation granule) clear
     if (MODE == 0) {
         // (position words < s all ones for both halves; every lane's later accesses read words
         // other lanes wrote: the workgroup is one wave, whose LDS ops complete in order)
@@ -4694,6 +4700,45 @@ hipError_t launch_jump_prep(const int32_t* counts, const BatchShape& sh, uint32_
     return hipGetLastError();
 }
 
+// The throughput kernel's launch tiers.  The host knows only the bound max_s of a batch's sample
+// counts, not the counts (no sync), and a bitmap sized for the bound caps the kernel's occupancy
+// whatever the pairs hold: 8960 B per one-wave workgroup at max_s = 1024 is 4 waves per SIMD
+// where the registers allow kSamplerRegWaves.  So sampler_kernel<0> is launched once per tier,
+// each launch over the whole grid with the LDS of its own range: tier t takes the pairs with s in
+// (s_hi[t-1], s_hi[t]] (every s >= 1 is in exactly one, the last one ends at max_s), every other
+// workgroup returns on its pair's count.  The ranges are the occupancy steps: w waves per SIMD
+// fit while the allocation (2 x (s_hi + 32) position words, in 1280-B granules) is at most
+// kLdsPerCu / (4 w) bytes -- s <= 768 at 6 waves, <= 928 at 5, <= 1248 at 4.  At most `limit`
+// launches (<= kSamplerMaxTiers): the steps from the highest occupancy down, then one launch for
+// the rest, sized for the bound as the single launch was; steps at or above max_s are not
+// launched, so a bound within the first step is one launch.  Returns the number of tiers.
+constexpr int kSamplerMaxTiers = 4;
+constexpr int kSamplerTiersAuto = 4;      // ERP_OPT_SAMPLER_TIERS = -1
+constexpr int kSamplerRegWaves = 6;       // sampler_kernel<0>: 79 VGPRs
+constexpr int kLdsPerCu = 160 * 1024;
+constexpr int kLdsGranule = 1280;         // bytes (scripts/dev/lds_oob.hip)
+struct SamplerTier {
+    int s_lo, s_hi, npos;                 // npos: position words per half-wave, >= s_hi + 32
+    size_t lds() const { return (size_t)npos * 2 * sizeof(uint32_t); }
+};
+// positions 0 .. s_hi + 31 (the lanes' clamp words) for each half-wave, the two halves together
+// rounded up to the granule (320 words)
+static int sampler_npos(int s_hi) { return (2 * (s_hi + 32) + 319) / 320 * 160; }
+static int sampler_tiers(int max_s, int limit, SamplerTier (&t)[kSamplerMaxTiers]) {
+    limit = std::min(std::max(limit, 1), kSamplerMaxTiers);
+    int n = 0, lo = 0;
+    for (int w = kSamplerRegWaves; w >= 1 && n < limit - 1; w--) {
+        const int bytes = kLdsPerCu / (4 * w) / kLdsGranule * kLdsGranule;
+        const int hi = bytes / 8 - 32;    // the largest s whose two halves fit
+        if (hi >= max_s) break;           // the bound fits this step: the last tier takes it
+        if (hi <= lo) continue;
+        t[n++] = SamplerTier{lo, hi, sampler_npos(hi)};
+        lo = hi;
+    }
+    t[n++] = SamplerTier{lo, max_s, sampler_npos(max_s)};  // (lo < max_s, or the only tier)
+    return n;
+}
+
 hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const uint32_t* polyQ,
                           const uint32_t* w0, const BatchShape& sh, double sample_frac,
                           const double* rtab, uint32_t* wins, uint32_t* selw, int32_t* flags,
@@ -4715,17 +4760,19 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
         const int lat = sh.sampler_lat >= 0 ? sh.sampler_lat
                                             : (long)nwaves * sh.n_pairs <= 1024 ? kSamplerLatMode : 0;
         const int mode = lat == 1 ? 2 : lat == 2 ? 3 : 0;
-        // the throughput kernel's position-major bitmap: positions 0 .. max_s + 31 (the lanes'
-        // clamp words) for each half-wave, the two halves together rounded up to the granule
-        // (320 words) -- the lane-major size within a granule (s up to 16 383: 2 x 16 480 words
-        // = 129 KB)
-        const int npos = (2 * (sh.max_s + 32) + 319) / 320 * 160;
-        const size_t shmem_pm = (size_t)npos * 2 * sizeof(uint32_t);
+        // the throughput kernel's position-major bitmap, one launch per tier (sampler_tiers
+        // above; the last tier's is the largest: the lane-major size within a granule, s up to
+        // 16 383: 2 x 16 480 words = 129 KB).  sh.sampler_tiers (ERP_OPT_SAMPLER_TIERS): -1
+        // automatic, 0 / 1 one bound-sized launch, n at most n launches
+        SamplerTier tiers[kSamplerMaxTiers];
+        const int ntiers = sampler_tiers(
+            sh.max_s, sh.sampler_tiers < 0 ? kSamplerTiersAuto : sh.sampler_tiers, tiers);
+        const size_t shmem_pm = tiers[ntiers - 1].lds();
         const void* fns[4] = {(const void*)sampler_kernel<0>, nullptr,
                               (const void*)sampler_kernel<2>, (const void*)sampler_kernel<3>};
-#define ERP_SAMPLER_LAUNCH(M, LDS, NALLOC)                                                     \
+#define ERP_SAMPLER_LAUNCH(M, LDS, NALLOC, S_LO, S_HI)                                         \
     ERP_LAUNCH(sampler_kernel<M>, dim3(nwaves, sh.n_pairs), dim3(64), LDS, st, counts, wins,   \
-               nwaves, sh.sel_words, sample_frac, rtab, selw, flags, NALLOC)
+               nwaves, sh.sel_words, sample_frac, rtab, selw, flags, NALLOC, S_LO, S_HI)
         // the split replay (sampler_split_kernel) where the launch has <= 256 workgroups of
         // 64 iterations (one pair at <= 16k iterations) and its 7 bitmaps fit the CU's LDS;
         // sh.sampler_split (ERP_OPT_SAMPLER_SPLIT) = 0 / 1 forces it off / on (when the LDS fits)
@@ -4743,9 +4790,20 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
         const hipError_t le = ensure_dyn_lds(fns[mode], mode == 0 ? shmem_pm : shmem);
         if (le != hipSuccess) return le;
         switch (mode) {
-            case 2: ERP_SAMPLER_LAUNCH(2, shmem, nwords); break;
-            case 3: ERP_SAMPLER_LAUNCH(3, shmem, nwords); break;
-            default: ERP_SAMPLER_LAUNCH(0, shmem_pm, npos); break;
+            case 2: ERP_SAMPLER_LAUNCH(2, shmem, nwords, 0, sh.max_s); break;
+            case 3: ERP_SAMPLER_LAUNCH(3, shmem, nwords, 0, sh.max_s); break;
+            default:
+                // every tier is launched, populated or not (the host does not know), on the
+                // one stream: a pair's selection words are complete before their consumers run
+                for (int t = 0; t < ntiers; t++) {
+                    // (what keeps a workgroup that passes the kernel's guard inside its LDS)
+                    if (tiers[t].s_hi + 32 > tiers[t].npos || tiers[t].lds() > shmem_pm ||
+                        tiers[t].s_lo != (t ? tiers[t - 1].s_hi : 0))
+                        return hipErrorInvalidValue;
+                    ERP_SAMPLER_LAUNCH(0, tiers[t].lds(), tiers[t].npos, tiers[t].s_lo,
+                                       tiers[t].s_hi);
+                }
+                break;
         }
 #undef ERP_SAMPLER_LAUNCH
     }

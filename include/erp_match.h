@@ -243,6 +243,9 @@ erp_status erp_ctx_set_graphs(erp_ctx* ctx, int32_t enable);
                           the block's positions first
    ERP_OPT_SAMPLER_SPLIT  split replay: -1 auto (<= 256 workgroups); 0 off; 1 on (where its
                           bitmaps fit the LDS)
+   ERP_OPT_SAMPLER_TIERS  throughput replay launches, each sizing its LDS bitmap for the pairs
+                          whose sample count falls in its range: -1 auto; 0 / 1 one launch sized
+                          for the batch's bound; n = 2 .. 4 at most n launches
    ERP_OPT_GRAM_TILES     32-iteration row tiles per Gram MFMA wave: 0 auto (2 once the launch
                           has >= 512 wide blocks), 1, 2
    ERP_OPT_ZOOM_LEVELS    the survivors' zoom levels 0 (default) .. 2
@@ -278,7 +281,8 @@ typedef enum erp_ctx_option {
     ERP_OPT_BOUND_RATIO = 10,
     ERP_OPT_DEBUG_STAGES = 11,
     ERP_OPT_DEBUG_SNAP = 12,
-    ERP_OPT_COUNT = 13
+    ERP_OPT_SAMPLER_TIERS = 13,
+    ERP_OPT_COUNT = 14
 } erp_ctx_option;
 /* ERP_INVALID_ARG for an unknown option or a value outside its range */
 erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value);

@@ -12,6 +12,8 @@
 //   V3  V2 with the magic shift as a compile-time constant per power-of-two range of d
 //   V4  V3 with the selection bit accumulated through the carry (v_and + v_add_co + v_addc)
 //   V5 - V7  the position-major bitmap and the whole replay in both layouts (further down)
+//   V10 V9, byte for byte, launched with a larger dynamic LDS allocation than it uses (the
+//       library's bound-sized one): what the allocation alone costs in occupancy
 // The real kernel (prefix and mixed blocks included) is timed beside it by sampler_sol.py through
 // the library's own stage timer.  Results are not the sampler's (the windows are random words):
 // this measures instruction cost, not parity.
@@ -297,8 +299,9 @@ __device__ __forceinline__ uint32_t sol_mixed(uint32_t (&ring)[31], uint32_t* bm
 }
 
 // V5 (POS, !FULL), V6 (POS, FULL), V7 (!POS, FULL), V8 / V9 (V5 / V6 + SPREAD).  nalloc: POS: position words per half (the
-// allocation is 2 * nalloc words); else lane-major words per lane
-template <bool POS, bool FULL, bool SPREAD>
+// allocation is 2 * nalloc words); else lane-major words per lane.  TAG only names the
+// instantiation (V10 = V9 under its own kernel name, so that counters tell the two apart)
+template <bool POS, bool FULL, bool SPREAD, int TAG = 0>
 __global__ __launch_bounds__(64) void sol_pm_kernel(const int32_t* __restrict__ counts, int nwaves,
                                                     double frac, const uint64_t* __restrict__ mtab,
                                                     uint32_t* __restrict__ out, int nbw, int nalloc) {
@@ -356,13 +359,16 @@ __global__ __launch_bounds__(64) void sol_pm_kernel(const int32_t* __restrict__ 
 extern "C" {
 // n_pairs pairs with counts[p] matches (device), iterations -> grid; mtab = the magic table
 // (device, d = 0 .. 65538: m_d | (l_d - 1) << 32); out = nbw words per lane (device).
-// Returns the kernel time in ms (hipEvent), or -1 on an error.
+// lds_bytes > 0: the dynamic LDS of the launch (>= what nalloc needs; V10), else derived from
+// nalloc.  Returns the kernel time in ms (hipEvent), or -1 on an error.
 float sol_run(int variant, const int32_t* counts, int n_pairs, int iters, double frac,
-              const uint64_t* mtab, uint32_t* out, int nbw, int nalloc, int reps) {
+              const uint64_t* mtab, uint32_t* out, int nbw, int nalloc, int reps, int lds_bytes) {
     const int nwaves = (iters + 63) / 64;
     // V5 / V6 / V8 / V9: nalloc position words per half-wave; else nalloc words per lane
-    const bool pm = variant == 5 || variant == 6 || variant == 8 || variant == 9;
-    const size_t shmem = pm ? (size_t)nalloc * 2 * 4 : (size_t)nalloc * 64 * 4;
+    const bool pm = variant == 5 || variant == 6 || variant == 8 || variant == 9 || variant == 10;
+    const size_t need = pm ? (size_t)nalloc * 2 * 4 : (size_t)nalloc * 64 * 4;
+    if (lds_bytes > 64 * 1024 || (lds_bytes > 0 && (size_t)lds_bytes < need)) return -1.f;
+    const size_t shmem = lds_bytes > 0 ? (size_t)lds_bytes : need;
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
@@ -373,12 +379,12 @@ float sol_run(int variant, const int32_t* counts, int n_pairs, int iters, double
                                              counts, nwaves, frac, mtab, out, nbw, nalloc); break;
             SOL_L(0) SOL_L(1) SOL_L(2) SOL_L(3) SOL_L(4)
 #undef SOL_L
-#define SOL_P(V, POS, FULL, SPREAD) case V: hipLaunchKernelGGL((sol_pm_kernel<POS, FULL, SPREAD>),  \
+#define SOL_P(V, POS, FULL, SPREAD, ...) case V: hipLaunchKernelGGL((sol_pm_kernel<POS, FULL, SPREAD, ##__VA_ARGS__>),  \
                                                                dim3(nwaves, n_pairs), dim3(64), shmem, 0,  \
                                                                counts, nwaves, frac, mtab, out, nbw,       \
                                                                nalloc); break;
             SOL_P(5, true, false, false) SOL_P(6, true, true, false) SOL_P(7, false, true, false)
-            SOL_P(8, true, false, true) SOL_P(9, true, true, true)
+            SOL_P(8, true, false, true) SOL_P(9, true, true, true) SOL_P(10, true, true, true, 1)
 #undef SOL_P
             default: return -1.f;
         }
