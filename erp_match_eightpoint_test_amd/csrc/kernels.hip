@@ -1230,22 +1230,21 @@ __global__ __launch_bounds__(256) void gram_limbs_kernel(const int32_t* __restri
 
 // Block = kGramWaves waves x 32 WT iterations (WT MFMA row tiles each); K loop over the pair's
 // selection words, two words (64 rows, 14 WT MFMAs per wave) per step.  Operands reach LDS only by
-// LDS-DMA (global_load_lds: the 14 KB limb images of the step's two words and the block's
+// LDS-DMA (buffer_load ... lds, GramDma: the 14 KB limb images of the step's two words and the block's
 // 2 x 32 WT kGramWaves selection words) into a ring of GramCfg::kRing slots, issued kRing - 1
 // steps ahead: the selection words stream from HBM once, and their latency is covered by the ring, not
 // by occupancy.  The limb images are read once per block and step, so the block's iteration
 // count sets the L2 -> LDS traffic per MFMA.  One raw
 // barrier per step after a counted vmcnt (never 0 in the loop); all LDS in one __shared__ array.
-// All 14 B fragments of a step are read before the first MFMA.  gram[p][36][iters] (SoA, the
-// eigen layout).
+// The step's 14 B fragments go through GramCfg::kQuads register quads (gram_step_frag): the
+// read of fragment f + kQuads - 1 is in flight before fragment f's MFMAs, each use waits with a
+// counted lgkmcnt, and only the step's last fragment waits for lgkmcnt(0).  gram[p][36][iters]
+// (SoA, the eigen layout).
 // (measured r02h, per 384-pair step: 4 waves / 3 blocks per CU 2.42 ms; 8 waves -- half the
 // L2 -> LDS image traffic -- 2.44; 6 waves 2.91 (a 6-wave block loads the SIMDs 2/2/1/1); all
-// 14 fragment reads issued before the first MFMA (ERP_GRAM_SCHED, 194 VGPRs) 2.55-2.63)
+// 14 fragment reads issued before the first MFMA (194 VGPRs, a wave per SIMD lost) 2.55-2.63)
 #ifndef ERP_GRAM_WAVES
 #define ERP_GRAM_WAVES 4
-#endif
-#ifndef ERP_GRAM_SCHED
-#define ERP_GRAM_SCHED 0
 #endif
 constexpr int kGramWaves = ERP_GRAM_WAVES;                      // waves per block
 constexpr int kGramWords = 2;                                   // selection words per K step
@@ -1256,6 +1255,12 @@ constexpr int kGramSelOff = kGramWords * kGramWordBytes;        // selection wor
 #endif
 #ifndef ERP_GRAM_MINBLOCKS
 #define ERP_GRAM_MINBLOCKS 3
+#endif
+#ifndef ERP_GRAM_QUADS1
+#define ERP_GRAM_QUADS1 4
+#endif
+#ifndef ERP_GRAM_QUADS2
+#define ERP_GRAM_QUADS2 2
 #endif
 constexpr int kGramPieces = kGramSelOff / 1024;                 // 1-KB limb pieces per step
 static_assert(kGramPieces == 14, "14 limb pieces of 1 KB per step");
@@ -1273,6 +1278,11 @@ struct GramCfg {
     static constexpr int kRing = WT == 1 ? ERP_GRAM_RING : 5;   // slots: DMAs kRing - 1 steps ahead
     static constexpr int kSlotBytes = kGramSelOff + kGramWords * kIters * 4;
     static constexpr int kMinBlocks = WT == 1 ? ERP_GRAM_MINBLOCKS : 2;
+    // B-fragment register quads of the K step's read pipeline (kQuads - 1 reads ahead of the
+    // MFMAs).  WT = 2 has 256 registers, 224 of them accumulators; WT = 1 keeps 3 waves per
+    // SIMD up to 168
+    static constexpr int kQuads = WT == 1 ? ERP_GRAM_QUADS1 : ERP_GRAM_QUADS2;
+    static_assert(kQuads >= 2 && kQuads <= kGramPieces, "at least one read ahead");
     static_assert(kRing >= 3, "ring");
     static_assert(kIters % 64 == 0 && kGramWords * kChunks % kGramWaves == 0 && kGramWaves <= 14,
                   "whole selection-word DMAs per wave");
@@ -1286,7 +1296,104 @@ constexpr int gram_piece0(int w) {
 }
 
 typedef __attribute__((address_space(3))) void* lds_vptr;
-typedef const __attribute__((address_space(1))) void* glb_vptr;
+// raw buffer descriptor word 3 on gfx9-family targets: DATA_FORMAT = 32-bit, no swizzle
+constexpr int kBufRsrcFlags = 0x00020000;
+
+// One wave's DMAs of a K step, op by op: the limb pieces gram_piece0(wv) .., the extra piece of
+// the first kGramPieces % kGramWaves waves, the wave's selection words.  Sources are buffer
+// descriptors in SGPRs (the pair's limb images; each selection-word stream of the wave) with a
+// scalar offset per DMA and one lane-offset register per transfer width -- no 64-bit per-lane
+// pointers beside the accumulators.  One vmcnt count per DMA; num_records = the bytes the pair
+// owns from the base on (every offset the loop forms stays inside them).
+template <int WT>
+struct GramDma {
+    using C = GramCfg<WT>;
+    static constexpr int kP = kGramPieces / kGramWaves;
+    static constexpr int kOps = kP + 1 + C::kSelPW;
+    __amdgpu_buffer_rsrc_t lrs, srs[C::kSelPW];
+    int8_t* lds;
+    int lane16, lane4, lp0, soff, nsteps;
+    bool extra;
+    template <int J>
+    __device__ __forceinline__ void op(int step) const {
+        const int sx = min(step, nsteps - 1);  // past the end: a harmless reload, never read
+        int8_t* slot = lds + (step % C::kRing) * C::kSlotBytes;
+        if constexpr (J <= kP) {
+            if (J < kP || extra)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(lrs, (lds_vptr)(slot + (lp0 + J) * 1024), 16,
+                                                         lane16, sx * kGramSelOff + (lp0 + J) * 1024,
+                                                         0, 0);
+        } else {
+            constexpr int e = J - kP - 1;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(srs[e], (lds_vptr)(slot + soff + e * 256), 4,
+                                                     lane4, sx * kGramWords * 256, 0, 0);
+        }
+    }
+    template <int J = 0>
+    __device__ __forceinline__ void all(int step) const {
+        if constexpr (J < kOps) {
+            op<J>(step);
+            all<J + 1>(step);
+        }
+    }
+};
+
+// B fragment F of a K step (1 KB apart from the LDS byte address `addr`) into a register quad.
+// The compiler does not count the asm's read, so every use goes through gram_frag_wait, which
+// carries the quad as an operand (the MFMAs cannot be scheduled above it).
+template <int F>
+__device__ __forceinline__ void gram_frag_read(i32x4& q, uint32_t addr) {
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(q) : "v"(addr), "n"(F * 1024) : "memory");
+}
+// at most N newer LDS reads may still be in flight (LDS returns in order; the compiler's own
+// selection-word reads and SMEM in the same counter only make the wait stricter)
+template <int N>
+__device__ __forceinline__ void gram_frag_wait(i32x4& q) {
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(q) : "n"(N));
+}
+// the step's first NQ reads, one per quad
+template <int NQ, int F = 0>
+__device__ __forceinline__ void gram_step_reads(i32x4 (&q)[NQ], uint32_t addr) {
+    if constexpr (F < NQ) {
+        gram_frag_read<F>(q[F], addr);
+        gram_step_reads<NQ, F + 1>(q, addr);
+    }
+}
+// Fragments F .. 13 of a step whose reads F .. F + NQ - 1 are in flight in q[f % NQ]: wait for
+// fragment F alone, run its WT MFMAs (word F / 7, column tile F % 7: the order of the plain
+// loop, exact int32 sums either way), then read fragment F + NQ into the quad they consumed.
+// The A operands of a word (16 selection bits -> 16 bytes: 4 bits -> 4 bytes by one 24-bit
+// multiply and a mask) are expanded when its first fragment comes up, not at the step's start:
+// the second word's reuse the first word's registers.
+template <int WT, int NQ, int F>
+__device__ __forceinline__ void gram_step_frag(i32x16 (&acc)[WT][kGramTiles],
+                                               uint32_t (&wsel)[WT][kGramWords],
+                                               const uint32_t (&wm)[kGramWords], i32x4 (&a)[WT],
+                                               i32x4 (&q)[NQ], uint32_t addr,
+                                               const GramDma<WT>& dma, int dstep) {
+    if constexpr (F < kGramPieces) {
+        if constexpr (F % kGramTiles == 0) {
+#pragma unroll
+            for (int w = 0; w < WT; w++) {
+                asm volatile("" : "+v"(wsel[w][F / kGramTiles]));  // not before the reads above
+                const uint32_t bits = wsel[w][F / kGramTiles] & wm[F / kGramTiles];
+#pragma unroll
+                for (int v = 0; v < 4; v++)
+                    a[w][v] = (int)((((bits >> (4 * v)) & 0xfu) * 0x00204081u) & 0x01010101u);
+            }
+        }
+        constexpr int kLeft = kGramPieces - 1 - F;  // reads issued after F's at the step's end
+        gram_frag_wait<(kLeft < NQ - 1 ? kLeft : NQ - 1)>(q[F % NQ]);
+#pragma unroll
+        for (int w = 0; w < WT; w++)
+            acc[w][F % kGramTiles] = __builtin_amdgcn_mfma_i32_32x32x32_i8(
+                a[w], q[F % NQ], acc[w][F % kGramTiles], 0, 0, 0);
+        if constexpr (F + NQ < kGramPieces) gram_frag_read<F + NQ>(q[F % NQ], addr);
+        // DMA op F of step dstep rides behind fragment F's MFMAs: its issue cost is covered
+        if constexpr (F < GramDma<WT>::kOps) dma.template op<F>(dstep);
+        gram_step_frag<WT, NQ, F + 1>(acc, wsel, wm, a, q, addr, dma, dstep);
+    }
+}
 
 template <int WT>
 __global__ __launch_bounds__(64 * kGramWaves, GramCfg<WT>::kMinBlocks) void gram_mfma_kernel(
@@ -1303,53 +1410,46 @@ __global__ __launch_bounds__(64 * kGramWaves, GramCfg<WT>::kMinBlocks) void gram
     // fetching them from HBM (identity when NB is not a multiple of 8)
     const int NB = gridDim.x;
     const int lbk = (NB & 7) ? (int)blockIdx.x : (int)((blockIdx.x & 7) * (NB >> 3) + (blockIdx.x >> 3));
-    const int p = lbk / nhb, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int p = lbk / nhb, tid = threadIdx.x, kl = tid & 63;  // kl: the K loop's lane id
+    // the wave index as a scalar: what depends on it alone (the wave's DMA pieces, their LDS
+    // and global bases, the branch on `extra`) then lives in SGPRs, not in the registers the
+    // accumulators leave free
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int M = counts[p];
-    const int s = (int)(M * sample_frac);
+    const int s = __builtin_amdgcn_readfirstlane((int)(M * sample_frac));  // uniform: an SGPR
     if (s < 1 || M < 2) return;
     const int hb = (lbk % nhb) * C::kIters;
     if (hb >= iters) return;  // uniform over the block
     const int nb = (M - 1) / 31 + 1;
     const int nsteps = (nb + kGramWords - 1) / kGramWords;  // words read: <= 2 nsteps - 1 <= nb < nbw
     const int h0 = hb + wv * 32 * WT;
-    const int r = lane & 31, hh = lane >> 5;
-    const int8_t* lg = limbs + (size_t)p * nbw * kGramWordBytes + lane * 16;
+    const int kr = kl & 31, kh = kl >> 5;
     // wave wv moves limb pieces gram_piece0(wv) .. + gram_pieces_of(wv) - 1 and the selection
     // words d = wv C::kSelPW + e: word d / C::kChunks of 64-iteration chunk d % C::kChunks
     // (chunks past the last iteration are clamped: their rows are never stored)
-    const int lp0 = [&] {
-        int v = 0;
+    GramDma<WT> dma;
+    dma.lds = lds;
+    dma.nsteps = nsteps;
+    dma.lane16 = kl * 16;
+    dma.lane4 = kl * 4;
+    dma.lrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<int8_t*>(limbs + (size_t)p * nbw * kGramWordBytes), 0, nbw * kGramWordBytes,
+        kBufRsrcFlags);
+    dma.lp0 = 0;
 #pragma unroll
-        for (int w = 0; w < kGramWaves; w++) v = (w == wv) ? gram_piece0(w) : v;
-        return v;
-    }();
-    const bool extra = wv < kGramPieces % kGramWaves;  // moves kGramPieces / W + 1 pieces
-    const uint32_t* sg[C::kSelPW];
+    for (int w = 0; w < kGramWaves; w++) dma.lp0 = (w == wv) ? gram_piece0(w) : dma.lp0;
+    dma.extra = wv < kGramPieces % kGramWaves;  // moves kGramPieces / W + 1 pieces
 #pragma unroll
     for (int e = 0; e < C::kSelPW; e++) {
         const int d = wv * C::kSelPW + e;
         const int chunk = min((hb >> 6) + d % C::kChunks, nwaves - 1);
-        sg[e] = selw + ((size_t)p * nwaves + chunk) * (size_t)nbw * 64 + lane +
-                (size_t)(d / C::kChunks) * 64;
+        dma.srs[e] = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint32_t*>(selw + ((size_t)p * nwaves + chunk) * (size_t)nbw * 64 +
+                                  (size_t)(d / C::kChunks) * 64),
+            0, (nbw - d / C::kChunks) * 256, kBufRsrcFlags);
     }
-    const int soff = kGramSelOff + wv * C::kSelPW * 256;
-    auto issue = [&](int step) {
-        const int sx = min(step, nsteps - 1);  // past the end: a harmless reload, never read
-        int8_t* slot = lds + (step % C::kRing) * C::kSlotBytes;
-        const int8_t* src = lg + (size_t)sx * kGramSelOff;
-#pragma unroll
-        for (int k = 0; k < kGramPieces / kGramWaves; k++)
-            __builtin_amdgcn_global_load_lds((glb_vptr)(src + (lp0 + k) * 1024),
-                                             (lds_vptr)(slot + (lp0 + k) * 1024), 16, 0, 0);
-        if (extra)
-            __builtin_amdgcn_global_load_lds(
-                (glb_vptr)(src + (lp0 + kGramPieces / kGramWaves) * 1024),
-                (lds_vptr)(slot + (lp0 + kGramPieces / kGramWaves) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int e = 0; e < C::kSelPW; e++)
-            __builtin_amdgcn_global_load_lds((glb_vptr)(sg[e] + (size_t)(sx * kGramWords) * 64),
-                                             (lds_vptr)(slot + soff + e * 256), 4, 0, 0);
-    };
+    dma.soff = kGramSelOff + wv * C::kSelPW * 256;
+    const bool extra = dma.extra;
     i32x16 acc[WT][kGramTiles];
 #pragma unroll
     for (int w = 0; w < WT; w++)
@@ -1358,8 +1458,9 @@ __global__ __launch_bounds__(64 * kGramWaves, GramCfg<WT>::kMinBlocks) void gram
 #pragma unroll
             for (int k = 0; k < 16; k++) acc[w][t][k] = 0;
 #pragma unroll
-    for (int k = 0; k < C::kRing - 1; k++) issue(k);
-    const int boff = r * 32 + (((hh ^ (r >> 3)) & 1) << 4);
+    for (int k = 0; k < C::kRing - 1; k++) dma.all(k);
+    const int boff = kr * 32 + (((kh ^ (kr >> 3)) & 1) << 4);
+    const int woff = kr * 4 + kh * 2;  // this lane's 16 selection bits in its row's word
     for (int st = 0; st < nsteps; st++) {
         // step st's DMAs retired: the C::kRing - 2 later steps may fly (pieces + 1 each)
         constexpr int kBase = kGramPieces / kGramWaves + C::kSelPW;
@@ -1367,49 +1468,33 @@ __global__ __launch_bounds__(64 * kGramWaves, GramCfg<WT>::kMinBlocks) void gram
         if (extra) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((kBase + 1) * (C::kRing - 2)) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kBase * (C::kRing - 2)) : "memory");
         __builtin_amdgcn_s_barrier();
-        issue(st + C::kRing - 1);  // into the slot every wave finished reading in step st - 1
         const int8_t* slot = lds + (st % C::kRing) * C::kSlotBytes;
-        // every B fragment of the step in flight at once (the MFMAs then wait on counted
-        // lgkmcnts): the step's LDS latency is exposed once, not once per fragment pair
-        i32x4 bf[kGramWords][kGramTiles];
-#pragma unroll
-        for (int i = 0; i < kGramWords; i++)
-#pragma unroll
-            for (int t = 0; t < kGramTiles; t++)
-                bf[i][t] = *reinterpret_cast<const i32x4*>(slot + i * kGramWordBytes +
-                                                           t * 32 * 32 + boff);
-        uint32_t wsel[WT][kGramWords];  // read after the fragments: one wait covers the step
+        // the step's selection words first (the compiler's own reads and wait: each lane takes
+        // the 16-bit half kh of its row's words), then the first C::kQuads B fragments: their
+        // latency runs under the selection words' wait and the A expansion
+        uint32_t wsel[WT][kGramWords];
 #pragma unroll
         for (int w = 0; w < WT; w++)
 #pragma unroll
             for (int i = 0; i < kGramWords; i++)
-                wsel[w][i] = reinterpret_cast<const uint32_t*>(slot + kGramSelOff)[
-                    i * C::kIters + (wv * WT + w) * 32 + r];
-        i32x4 a[WT][kGramWords];
-#pragma unroll
-        for (int w = 0; w < WT; w++)
-#pragma unroll
-            for (int i = 0; i < kGramWords; i++) {
-                const uint32_t wm = (st * kGramWords + i < nb) ? 0xffffu : 0u;  // words past nb
-                const uint32_t bits = (wsel[w][i] >> (16 * hh)) & wm;
-#pragma unroll
-                for (int v = 0; v < 4; v++)
-                    a[w][i][v] = (int)((((bits >> (4 * v)) & 0xfu) * 0x00204081u) & 0x01010101u);
-            }
-#if ERP_GRAM_SCHED
-        __builtin_amdgcn_sched_group_barrier(0x100, kGramWords * (kGramTiles + 1), 0);  // LDS reads
-        __builtin_amdgcn_sched_group_barrier(0x002, 4 * kGramWords * 4, 0);            // VALU
-        __builtin_amdgcn_sched_group_barrier(0x008, kGramWords * kGramTiles, 0);       // MFMAs
-#endif
-#pragma unroll
-        for (int i = 0; i < kGramWords; i++)
-#pragma unroll
-            for (int t = 0; t < kGramTiles; t++)
-#pragma unroll
-                for (int w = 0; w < WT; w++)
-                    acc[w][t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[w][i], bf[i][t], acc[w][t], 0, 0, 0);
+                wsel[w][i] = *reinterpret_cast<const uint16_t*>(
+                    slot + kGramSelOff + (i * C::kIters + (wv * WT + w) * 32) * 4 + woff);
+        const uint32_t wm[kGramWords] = {0xffffu,  // words past nb (the last step's second) masked
+                                         (st * kGramWords + 1 < nb) ? 0xffffu : 0u};
+        static_assert(kGramWords == 2, "wm");
+        const uint32_t baddr = (uint32_t)(uintptr_t)(lds_vptr)(slot + boff);
+        i32x4 bq[C::kQuads];
+        gram_step_reads<C::kQuads>(bq, baddr);
+        // the DMAs of step st + C::kRing - 1 (into the slot every wave finished reading in step
+        // st - 1) are issued one by one behind the first fragments' MFMAs
+        i32x4 a[WT];
+        gram_step_frag<WT, C::kQuads, 0>(acc, wsel, wm, a, bq, baddr, dma, st + C::kRing - 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the ring's tail DMAs
+    // the epilogue's lane ids from the hardware lane count, not from the K loop's: nothing
+    // lane-dependent then stays live across the loop beside what the loop itself reads
+    const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int r = lane & 31, hh = lane >> 5;
     // recombine: row = (k & 3) + 8 (k >> 2) + 4 hh; entry r from tiles 0..5 of this lane,
     // entries 32..35 from tile 6 (lane 4 limb + e)
     double* go = gram + (size_t)p * 36 * iters;
