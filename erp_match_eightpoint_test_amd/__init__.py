@@ -24,11 +24,11 @@ import ctypes as C
 import numpy as np
 
 from . import capi, synth
-from .capi import (DMATCH_DTYPE, HYP_DTYPE, RESULT_DTYPE, Context, ErpError, check,
-                   default_cfg)
+from .capi import (DMATCH_DTYPE, HYP_DTYPE, RESULT_DTYPE, Context, ErpError, RandStream, check,
+                   default_cfg, process_rand_stream)
 
 __all__ = ["feature_matcher", "eight_point", "erp_rotation", "spherical_surf", "epipolar_tool",
-           "PairBatchRunner", "Context", "ErpError",
+           "PairBatchRunner", "Context", "ErpError", "RandStream", "process_rand_stream",
            "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "results_to_numpy",
            "hyps_to_numpy", "synth", "capi"]
 
@@ -161,12 +161,18 @@ class feature_matcher:  # noqa: N801  (reference class name)
 
 
 class eight_point:  # noqa: N801  (reference class name)
-    """eight_point (src/eight_point.hpp:8-28).  ``cfg`` holds the reference constants."""
+    """eight_point (src/eight_point.hpp:8-28).  ``cfg`` holds the reference constants.
+    ``stream``: a RandStream that find / initial_guess draw from and advance, as the reference's
+    finds share the process-global rand() (``stream=process_rand_stream()``); the default,
+    None, starts every call at cfg.seed / cfg.offset."""
 
-    def __init__(self, device: int = 0, ctx: Context | None = None, **cfg):
+    def __init__(self, device: int = 0, ctx: Context | None = None,
+                 stream: RandStream | None = None, **cfg):
         self.ctx = ctx or Context(device)
         self.cfg = default_cfg(**cfg)
         self.last_result = None
+        if stream is not None:
+            self.ctx.set_rand_stream(stream)
 
     def find(self, im_width: int, im_height: int, key_left, key_right, match_size: int | None = None):
         """-> (R_vec_out (3,) float32, T_vec_out (3,) float32); raises ErpError on the
@@ -245,7 +251,9 @@ class epipolar_tool:  # noqa: N801  (reference class name)
 
     def __init__(self, left_key, right_key, im_width: int, im_height: int, output_width: int,
                  output_height: int, test_key_num: int, seed: int = 1, offset: int = 0,
-                 device: int = 0, ctx: Context | None = None):
+                 device: int = 0, ctx: Context | None = None, stream: RandStream | None = None):
+        """stream: the constructor's shuffle draws from this RandStream and advances it by
+        match_size - 1 (seed / offset are then the stream's position at that moment)"""
         self.ctx = ctx or Context(device)
         self.left_key, self.right_key = _keys_host(left_key), _keys_host(right_key)
         if self.left_key.shape != self.right_key.shape:
@@ -259,6 +267,10 @@ class epipolar_tool:  # noqa: N801  (reference class name)
             raise ErpError(capi.ERP_INVALID_ARG,
                            "epipolar_tool: need 0 <= test_key_num <= min(7, match_size)")
         # the constructor's choice (src/epipolar_tool.cpp:13-16), available before any draw
+        if stream is not None:
+            self.seed, self.offset = stream.get()
+            self.random_idx = stream.shuffle_prefix(self.match_size, self.n_key)
+            return
         self.random_idx = np.zeros(self.n_key, np.int32)
         check(self.ctx.L.erp_random_shuffle_prefix(self.seed, self.offset, self.match_size,
                                                    self.n_key, _np_ptr(self.random_idx)),
@@ -270,6 +282,19 @@ class epipolar_tool:  # noqa: N801  (reference class name)
         dev = torch.device(f"cuda:{self.ctx.device}")
         out = torch.empty((self.epipole_mat_height, self.epipole_mat_width, 3), dtype=torch.uint8,
                           device=dev)
+        # the draw repeats the constructor's choice at its recorded (seed, offset): a rand
+        # stream attached to the context must not be consumed a second time
+        attached = self.ctx.rand_stream
+        if attached is not None:
+            self.ctx.set_rand_stream(None)
+        try:
+            return self._draw(E, out, dev)
+        finally:
+            if attached is not None:
+                self.ctx.set_rand_stream(attached)
+
+    def _draw(self, E, out, dev):
+        import torch
         check(self.ctx.L.erp_epipolar_draw_dev(
             self.ctx.h, _np_ptr(self.left_key), _np_ptr(self.right_key), self.match_size,
             self.im_width, self.im_height, self.epipole_mat_width, self.epipole_mat_height,
@@ -600,8 +625,11 @@ class PairBatchRunner:
     """
 
     def __init__(self, device: int = 0, ctx: Context | None = None, reuse_outputs: bool = False,
-                 **cfg):
-        """reuse_outputs: run() hands back the SAME output tensors for the same shape (copy them
+                 stream: RandStream | None = None, **cfg):
+        """stream: a RandStream (not a HIP stream) the runs draw from and advance, pair after
+        pair as the reference's drivers do on the process-global rand(); None: every pair of
+        every run starts at cfg.seed / cfg.offset.
+        reuse_outputs: run() hands back the SAME output tensors for the same shape (copy them
         before the next call) -- what a HIP-graph replay (Context.set_graphs) needs, since the
         captured graph bakes the output pointers in"""
         self.ctx = ctx or Context(device)
@@ -609,6 +637,8 @@ class PairBatchRunner:
         self.device = self.ctx.device
         self.reuse_outputs = reuse_outputs
         self._outs = {}
+        if stream is not None:
+            self.ctx.set_rand_stream(stream)
 
     def reserve(self, n_pairs: int, max_nq: int, max_nt: int):
         check(self.ctx.L.erp_ctx_reserve(self.ctx.h, n_pairs, max_nq, max_nt, self.cfg.iters),

@@ -19,12 +19,12 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ERP_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip", "surf.hip", "surf_api.hip", "viz.hip",
-           "image_batch.hip",
+           "image_batch.hip", "rand_stream.hip",
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
-           "erp_launch.hpp"]
+           "erp_launch.hpp", "erp_jump_poly.hpp"]
 PUBLIC_HEADERS = ["erp_match.h", os.path.join("erp", "feature_matcher.hpp"),
-                  os.path.join("erp", "eight_point.hpp")]
+                  os.path.join("erp", "eight_point.hpp"), os.path.join("erp", "rand_stream.hpp")]
 
 # -ffp-contract=off: the matcher's flann::L2 order, the ratio test and the consensus
 # distances must round exactly like the reference's x86-64 code (no FMA contraction).
@@ -109,20 +109,32 @@ def build(force: bool = False, verbose: bool = False, lib_path: str = LIB_PATH,
 
 DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "class_api_driver.cpp")
 DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "class_api_driver")
+# two successive erp::eight_point objects on erp::rand_stream::process()
+STREAM_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "rand_stream_driver.cpp")
+STREAM_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "rand_stream_driver")
+
+
+def _build_cpp_driver(src: str, out: str, force: bool) -> str:
+    if (not force and os.path.exists(out)
+            and os.path.getmtime(out) >= max(os.path.getmtime(src), os.path.getmtime(LIB_PATH))):
+        return out
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), src,
+                    "-o", out, "-L", LIB_DIR, "-lerp_match", f"-Wl,-rpath,{LIB_DIR}",
+                    "-Wl,-rpath,$ORIGIN/../../erp_match_eightpoint_test_amd/lib",
+                    "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    return out
 
 
 def build_driver(force: bool = False) -> str:
-    """the C++ class-API driver (tests/cpp): host code only, g++ against liberp_match.so -- the
-    link a reference maintainer would do."""
-    if (not force and os.path.exists(DRIVER_BIN)
-            and os.path.getmtime(DRIVER_BIN) >= max(os.path.getmtime(DRIVER_SRC),
-                                                    os.path.getmtime(LIB_PATH))):
-        return DRIVER_BIN
-    subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), DRIVER_SRC,
-                    "-o", DRIVER_BIN, "-L", LIB_DIR, "-lerp_match", f"-Wl,-rpath,{LIB_DIR}",
-                    "-Wl,-rpath,$ORIGIN/../../erp_match_eightpoint_test_amd/lib",
-                    "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return DRIVER_BIN
+    """the C++ class-API drivers (tests/cpp): host code only, g++ against liberp_match.so -- the
+    link a reference maintainer would do.  Returns the class API
+    driver; build_stream_driver() the rand stream one."""
+    _build_cpp_driver(STREAM_DRIVER_SRC, STREAM_DRIVER_BIN, force)
+    return _build_cpp_driver(DRIVER_SRC, DRIVER_BIN, force)
+
+
+def build_stream_driver(force: bool = False) -> str:
+    return _build_cpp_driver(STREAM_DRIVER_SRC, STREAM_DRIVER_BIN, force)
 
 
 if __name__ == "__main__":

@@ -96,7 +96,11 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_random_shuffle_prefix", "erp_ctx_set_graphs", "erp_debug_check_pads", "erp_debug_lip_counters",
             "erp_debug_snapshot", "erp_ctx_set_option", "erp_ctx_get_option",
             "erp_debug_set_alloc_pad", "erp_pack_band_features_dev",
-            "erp_image_pairs_features_dev", "erp_image_pairs_run"]
+            "erp_image_pairs_features_dev", "erp_image_pairs_run",
+            "erp_rand_stream_create", "erp_rand_stream_destroy", "erp_rand_stream_get",
+            "erp_rand_stream_set", "erp_rand_stream_advance", "erp_rand_stream_process",
+            "erp_ctx_set_rand_stream", "erp_ctx_get_rand_stream",
+            "erp_rand_stream_shuffle_prefix"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -234,6 +238,15 @@ def load(build_if_missing: bool = False):
                                       C.POINTER(SurfParams), C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(PackedPairs), C.c_float, C.POINTER(RansacCfg),
                                       C.POINTER(BatchOutputs), C.POINTER(ImageBatchInfo), P]
+    L.erp_rand_stream_create.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(P)]
+    L.erp_rand_stream_destroy.argtypes = [P]
+    L.erp_rand_stream_get.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.erp_rand_stream_set.argtypes = [P, C.c_uint32, C.c_uint64]
+    L.erp_rand_stream_advance.argtypes = [P, C.c_uint64]
+    L.erp_rand_stream_process.argtypes = [C.c_int32, C.POINTER(P)]
+    L.erp_ctx_set_rand_stream.argtypes = [P, P]
+    L.erp_ctx_get_rand_stream.argtypes = [P, C.POINTER(P)]
+    L.erp_rand_stream_shuffle_prefix.argtypes = [P, C.c_int32, C.c_int32, P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]
@@ -254,6 +267,65 @@ def check(status: int, where: str):
         raise ErpError(status, where)
 
 
+class RandStream:
+    """erp_rand_stream: the glibc rand() stream continued from call to call (include/erp_match.h
+    "rand stream").  Host only until a GPU call uses it.  Attach it with
+    Context.set_rand_stream or the ``stream=`` keyword of eight_point / epipolar_tool /
+    PairBatchRunner; calls take it in call order."""
+
+    def __init__(self, seed: int = 1, offset: int = 0, _handle=None):
+        self.L = load()
+        self.owned = _handle is None
+        self.h = P() if self.owned else _handle
+        if self.owned:
+            check(self.L.erp_rand_stream_create(seed, offset, C.byref(self.h)),
+                  "erp_rand_stream_create")
+
+    def get(self) -> tuple:
+        """(seed, draws consumed), after the stream's last device update"""
+        seed, draws = C.c_uint32(), C.c_uint64()
+        check(self.L.erp_rand_stream_get(self.h, C.byref(seed), C.byref(draws)),
+              "erp_rand_stream_get")
+        return int(seed.value), int(draws.value)
+
+    @property
+    def draws(self) -> int:
+        return self.get()[1]
+
+    def set(self, seed: int, offset: int):
+        check(self.L.erp_rand_stream_set(self.h, seed, offset), "erp_rand_stream_set")
+
+    def advance(self, n: int):
+        """skip n draws (rand() calls made elsewhere, e.g. by FLANN)"""
+        check(self.L.erp_rand_stream_advance(self.h, n), "erp_rand_stream_advance")
+
+    def shuffle_prefix(self, m: int, n: int) -> np.ndarray:
+        """the first n of std::random_shuffle(iota(m)) on the stream; consumes m - 1 draws"""
+        out = np.zeros(max(n, 1), np.int32)
+        check(self.L.erp_rand_stream_shuffle_prefix(self.h, m, n, out.ctypes.data_as(P)),
+              "erp_rand_stream_shuffle_prefix")
+        return out[:n]
+
+    def close(self):
+        if self.owned and self.h:
+            self.L.erp_rand_stream_destroy(self.h)
+        self.h = P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def process_rand_stream(device: int = 0) -> RandStream:
+    """the process-wide stream of a device, at (1, 0) in a fresh process (glibc's global rand()
+    state); never destroyed"""
+    h = P()
+    check(load().erp_rand_stream_process(device, C.byref(h)), "erp_rand_stream_process")
+    return RandStream(_handle=h)
+
+
 class Context:
     """erp_ctx: one per device/thread; owns the grow-only device scratch."""
 
@@ -262,6 +334,7 @@ class Context:
         self.h = P()
         check(self.L.erp_ctx_create(device, C.byref(self.h)), "erp_ctx_create")
         self.device = device
+        self.rand_stream = None
 
     def set_profiling(self, enable: bool = True):
         check(self.L.erp_ctx_set_profiling(self.h, 1 if enable else 0), "set_profiling")
@@ -283,6 +356,13 @@ class Context:
         v = C.c_int32()
         check(self.L.erp_ctx_get_option(self.h, OPTIONS[name], C.byref(v)), f"get_option({name})")
         return int(v.value)
+
+    def set_rand_stream(self, stream: "RandStream | None"):
+        """erp_ctx_set_rand_stream: the consuming calls on this context draw from ``stream`` and
+        advance it (None detaches: cfg.seed / cfg.offset again).  Keeps the stream alive."""
+        check(self.L.erp_ctx_set_rand_stream(self.h, stream.h if stream is not None else None),
+              "set_rand_stream")
+        self.rand_stream = stream
 
     def stage_times(self) -> dict:
         """{stage: (total_ms, launches)} since the last call (syncs on the recorded events)."""

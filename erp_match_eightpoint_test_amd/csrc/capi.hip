@@ -79,29 +79,31 @@ bool ensure(DevBuf& b, size_t bytes) {
 }  // namespace
 
 // (global linkage: viz.hip shuffles on the same stream)
-// glibc rand() window before draw `offset` of a stream seeded with `seed` (host, sequential;
-// same recurrence the kernels jump along).  31 words r[n-31..n-1].
+// glibc rand() window before draw `offset` of a stream seeded with `seed` (host; same
+// recurrence the kernels jump along).  31 words r[n-31..n-1].  Small offsets step the
+// recurrence; above kSeqOffsets the window before draw 0 is moved on by x^offset mod P
+// (rand_stream.hip glibc_poly_pow: ~128 products of 31 x 31 words whatever the offset).
+constexpr uint64_t kSeqOffsets = 4096;
 void host_glibc_window(uint32_t seed, uint64_t offset, uint32_t out[31]) {
-    int32_t r0[34];
-    if (seed == 0) seed = 1;
-    r0[0] = (int32_t)seed;
-    for (int i = 1; i < 31; i++) {
-        const long hi = r0[i - 1] / 127773, lo = r0[i - 1] % 127773;
-        long word = 16807 * lo - 2836 * hi;
-        if (word < 0) word += 2147483647;
-        r0[i] = (int32_t)word;
-    }
-    for (int i = 31; i < 34; i++) r0[i] = r0[i - 31];
-    uint32_t ring[34];
-    for (int i = 0; i < 34; i++) ring[i] = (uint32_t)r0[i];
-    uint64_t pos = 34;                    // absolute index of the next word
-    const uint64_t end = 344 + offset;    // draw k uses word k + 344
-    for (; pos < end; pos++) {
-        const uint32_t s = (uint32_t)(pos % 34);
-        ring[s] = ring[(pos - 3) % 34] + ring[(pos - 31) % 34];
-    }
-    for (int j = 0; j < 31; j++) out[j] = ring[(end - 31 + j) % 34];
+    if (offset <= kSeqOffsets) return erp::glibc_window_seq(seed, offset, out);
+    erp::glibc_window_seq(seed, 0, out);
+    erp::glibc_window_jump(out, offset);
 }
+
+// A rand stream (include/erp_match.h): host state until the first GPU call that uses it, then
+// the device copy d_state (erp_kernels.hpp kStream*) is the authoritative one.
+struct erp_rand_stream {
+    std::mutex mu;            // calls take the stream in the order they lock it
+    uint32_t seed = 1;
+    uint64_t draws = 0;
+    uint32_t win[31] = {};
+    int device = -1;          // the device of d_state (a process stream: fixed from the start)
+    uint32_t* d_state = nullptr;
+    // recorded right after the last kernel that touched d_state; the next one waits for it
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    bool process_owned = false;
+};
 
 struct erp_ctx {
     int device = 0;
@@ -123,7 +125,13 @@ struct erp_ctx {
     DevBuf zsel;              // consensus zoom: the survivors' rank-window bins (level 1 grid)
     DevBuf part, part1, pu, ccount, cand, bsel, edges, gfin, matches, counts, flags, pts, polyR, polyQ, idx, gram, hyps, rv, tv, kcount, tmean,
         sortbuf, w0, off, wh, results, in_a, in_b, in_c, in_d, dscale, lb, ub, surv, nsurv, wins,
-        rtab, limbs, tsplit, ovf, remap_scr, vchunk, lipref, inl, hlite;
+        rtab, limbs, tsplit, ovf, remap_scr, vchunk, lipref, inl, hlite,
+        w0s;                  // per-pair start windows [P][31] of a call on a rand stream
+    // the attached rand stream (erp_ctx_set_rand_stream; not owned) and whether the current
+    // enqueue is being captured into a graph (the stream's event is then handled around the
+    // graph launch: an event inside a captured region orders nothing outside it)
+    erp_rand_stream* rs = nullptr;
+    bool rs_capture = false;
     DevBuf extra[18];         // erp_ctx_scratch_internal slots (1-11 SURF, 12 viz, 13-17 image batch)
     // route options (erp_ctx_set_option; include/erp_match.h documents each, defaults below)
     int32_t opt[ERP_OPT_COUNT] = {
@@ -186,7 +194,7 @@ const CtxBuf kCtxBufs[] = {
     ERP_B(in_d, 0), ERP_B(dscale, 1), ERP_B(lb, 1), ERP_B(ub, 1), ERP_B(surv, 1),
     ERP_B(nsurv, 1), ERP_B(wins, 1), ERP_B(rtab, 1), ERP_B(limbs, 1), ERP_B(tsplit, 1),
     ERP_B(ovf, 1), ERP_B(remap_scr, 0), ERP_B(vchunk, 1), ERP_B(lipref, 1), ERP_B(inl, 1),
-    ERP_B(hlite, 1)};
+    ERP_B(hlite, 1), ERP_B(w0s, 1)};
 #undef ERP_B
 
 #define ERP_CK(x)                                         \
@@ -333,6 +341,7 @@ erp_status erp_ctx_create(int32_t device, erp_ctx** out) {
     if (!c) return ERP_OUT_OF_MEMORY;
     c->device = device;
     erp::init_constants();
+    erp::init_stream_constants();
     *out = c;
     return ERP_OK;
 }
@@ -505,6 +514,80 @@ erp_status upload_w0(erp_ctx* c, const erp_ransac_cfg* cfg, hipStream_t st) {
     return ERP_OK;
 }
 
+// ---- rand stream: device side (the C entry points are at the end of this file) ----
+
+// the stream's state into device memory on `device` (once; blocking, so never inside a capture)
+erp_status rs_to_device(erp_rand_stream* s, int device) {
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->d_state) return s->device == device ? ERP_OK : ERP_INVALID_ARG;
+    if (s->device >= 0 && s->device != device) return ERP_INVALID_ARG;  // a process stream
+    uint32_t h[erp::kStreamStateWords] = {};
+    memcpy(h + erp::kStreamWin, s->win, sizeof(s->win));
+    h[erp::kStreamSeed] = s->seed;
+    memcpy(h + erp::kStreamDraws, &s->draws, 8);
+    uint32_t* d = nullptr;
+    if (hipMalloc(&d, sizeof(h)) != hipSuccess) return ERP_OUT_OF_MEMORY;
+    hipEvent_t ev = nullptr;
+    if (hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
+        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipFree(d);
+        return ERP_HIP_ERROR;
+    }
+    s->d_state = d;
+    s->ev = ev;
+    s->device = device;
+    return ERP_OK;
+}
+
+// a stream's turn on HIP stream st: holds the stream's lock, makes st wait for the last kernel
+// that touched the state, and on exit records the end of this turn's kernels
+struct RsTurn {
+    erp_rand_stream* s;
+    hipStream_t st;
+    RsTurn(erp_rand_stream* s_, hipStream_t st_) : s(s_), st(st_) {
+        s->mu.lock();
+        if (s->pending) (void)hipStreamWaitEvent(st, s->ev, 0);
+    }
+    ~RsTurn() {
+        if (hipEventRecord(s->ev, st) == hipSuccess) s->pending = true;
+        s->mu.unlock();
+    }
+    RsTurn(const RsTurn&) = delete;
+    RsTurn& operator=(const RsTurn&) = delete;
+};
+
+// a consuming call's preparation, before anything is enqueued or captured: no Philox on a
+// stream, the per-pair windows' buffer, the state on the context's device
+erp_status stream_prepare(erp_ctx* c, const erp_ransac_cfg* cfg, size_t n_pairs) {
+    if (cfg->sampler != ERP_SAMPLER_GLIBC) return ERP_INVALID_ARG;
+    if (!ensure(c->w0s, n_pairs * 31 * 4) || !erp::stream_tables_ready())
+        return ERP_OUT_OF_MEMORY;
+    return rs_to_device(c->rs, c->device);
+}
+
+// the consuming launch (counts[P] final): every pair's start window, the state advanced.  The
+// stream's event is recorded right here, not at the end of the call, so that calls on other
+// contexts that share the stream wait for these two kernels only.
+erp_status stream_assign(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_cfg* cfg,
+                         hipStream_t st) {
+    erp_rand_stream* s = c->rs;
+    StageTimer _t(c, ERP_STAGE_JUMP_PREP, st);
+    if (c->rs_capture) {  // (the graph launch takes the stream's turn: erp_pair_batch_run)
+        ERP_CK(erp::launch_stream_assign((int32_t*)c->counts.p, sh.n_pairs, cfg->iters,
+                                         cfg->sample_frac, s->d_state, (uint32_t*)c->w0s.p, st));
+        return ERP_OK;
+    }
+    RsTurn turn(s, st);
+    ERP_CK(erp::launch_stream_assign((int32_t*)c->counts.p, sh.n_pairs, cfg->iters,
+                                     cfg->sample_frac, s->d_state, (uint32_t*)c->w0s.p, st));
+    return ERP_OK;
+}
+
+// the start windows of a call: the stream's per-pair ones, or cfg's (seed, offset) for all
+erp_status prepare_w0(erp_ctx* c, const erp_ransac_cfg* cfg, size_t n_pairs, hipStream_t st) {
+    return c->rs ? stream_prepare(c, cfg, n_pairs) : upload_w0(c, cfg, st);
+}
+
 bool cfg_ok(const erp_ransac_cfg* cfg) {
     return cfg && cfg->iters >= 1 &&
            (cfg->sampler == ERP_SAMPLER_GLIBC || cfg->sampler == ERP_SAMPLER_PHILOX) &&
@@ -545,9 +628,13 @@ bool use_lite(const erp_ransac_cfg* cfg, const erp_batch_outputs* out) {
 }
 // estimator stages after counts/pts are in place (lite: the estimates in the lite layout)
 erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ransac_cfg* cfg,
-                          const erp_batch_outputs* out, hipStream_t st, bool lite = false) {
+                          const erp_batch_outputs* out, hipStream_t st, bool lite = false,
+                          bool on_stream = false) {
     erp_ctx* ctx = c;
     erp::BatchShape sh = sh_in;  // + the sampler / Gram route options
+    // the glibc start windows: one per pair from the rand stream (stream_assign), or cfg's
+    const uint32_t* w0 = (const uint32_t*)(on_stream ? c->w0s.p : c->w0.p);
+    sh.w0_stride = on_stream ? 31 : 0;
     sh.sampler_lat = c->opt[ERP_OPT_SAMPLER_LAT];
     sh.sampler_split = c->opt[ERP_OPT_SAMPLER_SPLIT];
     sh.gram_tiles = c->opt[ERP_OPT_GRAM_TILES];
@@ -572,13 +659,13 @@ erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ra
         if (c->opt[ERP_OPT_DEBUG_STAGES] & 2) {
             StageTimer _t(ctx, ERP_STAGE_WINDOWS, st);
             ERP_CK(erp::launch_sampler(counts, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p,
-                                       (uint32_t*)c->w0.p, sh, cfg->sample_frac, rtab,
+                                       w0, sh, cfg->sample_frac, rtab,
                                        (uint32_t*)c->wins.p, (uint32_t*)c->idx.p, flags, st, 0));
         }
         if (c->opt[ERP_OPT_DEBUG_STAGES] & 4) {
             StageTimer _t(ctx, ERP_STAGE_SAMPLER, st);
             ERP_CK(erp::launch_sampler(counts, (uint32_t*)c->polyR.p, (uint32_t*)c->polyQ.p,
-                                       (uint32_t*)c->w0.p, sh, cfg->sample_frac, rtab,
+                                       w0, sh, cfg->sample_frac, rtab,
                                        (uint32_t*)c->wins.p, (uint32_t*)c->idx.p, flags, st, 1));
         }
     }
@@ -745,7 +832,10 @@ erp_status run_consensus(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac
 erp_status run_estimator(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_cfg* cfg,
                          const erp_batch_outputs* out, erp_pair_result* results, hipStream_t st) {
     const bool lite = use_lite(cfg, out);
-    erp_status es = run_hypotheses(c, sh, cfg, out, st, lite);
+    // (every caller is a consuming entry point: include/erp_match.h "rand stream")
+    erp_status es = c->rs ? stream_assign(c, sh, cfg, st) : ERP_OK;
+    if (es != ERP_OK) return es;
+    es = run_hypotheses(c, sh, cfg, out, st, lite, c->rs != nullptr);
     if (es != ERP_OK) return es;
     if (!(c->opt[ERP_OPT_DEBUG_STAGES] & 16)) return ERP_OK;
     return run_consensus(c, sh, cfg, out, results, st, true, 0, 0, 1, nullptr, nullptr, nullptr,
@@ -864,6 +954,8 @@ std::vector<uint8_t> graph_key(const erp_ctx* c, const erp_pair_batch* b, float 
     key_put(k, ratio);
     key_put(k, c->matcher);
     key_put(k, c->opt);
+    key_put(k, c->rs);  // the attached rand stream and its device state
+    key_put(k, c->rs ? c->rs->d_state : nullptr);
     for (const CtxBuf& b : kCtxBufs)
         if (b.graph) key_put(k, (c->*b.m).p);
     return k;
@@ -934,7 +1026,7 @@ erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio
     }
     erp_status es = ensure_estimator(ctx, sh, out);
     if (es != ERP_OK) return es;
-    es = upload_w0(ctx, cfg, st);
+    es = prepare_w0(ctx, cfg, (size_t)sh.n_pairs, st);
     if (es != ERP_OK) return es;
     if (cfg->inlier_thr > 0.0f && !ensure(ctx->inl, erp::inlier_scratch_bytes(sh)))
         return ERP_OUT_OF_MEMORY;
@@ -944,18 +1036,36 @@ erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (st != nullptr) ERP_CK(hipStreamIsCapturing(st, &cap));
     if (!ctx->use_graphs || ctx->profiling || st == nullptr || ctx->opt[ERP_OPT_DEBUG_SNAP] ||
-        cap != hipStreamCaptureStatusNone)
-        return batch_enqueue(ctx, b, ratio, cfg, out, sh, matches, st);
-    // graph replay: the same call (structs, buffers, scratch) as a captured one -> one launch
+        cap != hipStreamCaptureStatusNone) {
+        // (inside the caller's own capture the stream's event cannot order anything: the
+        // caller's graph then owns the order of the calls that share the stream)
+        ctx->rs_capture = cap != hipStreamCaptureStatusNone;
+        es = batch_enqueue(ctx, b, ratio, cfg, out, sh, matches, st);
+        ctx->rs_capture = false;
+        return es;
+    }
+    // graph replay: the same call (structs, buffers, scratch) as a captured one -> one launch.
+    // On a rand stream the state and the per-pair windows sit at fixed device addresses, so a
+    // replay continues the stream; the whole graph launch is the stream's turn.
+    auto launch = [&](hipGraphExec_t exec) -> erp_status {
+        if (!ctx->rs) {
+            ERP_CK(hipGraphLaunch(exec, st));
+            return ERP_OK;
+        }
+        RsTurn turn(ctx->rs, st);
+        ERP_CK(hipGraphLaunch(exec, st));
+        return ERP_OK;
+    };
     std::vector<uint8_t> key = graph_key(ctx, b, ratio, cfg, out);
     for (auto& g : ctx->graphs)
         if (g.key == key) {
             g.used = ++ctx->graph_clock;
-            ERP_CK(hipGraphLaunch(g.exec, st));
-            return ERP_OK;
+            return launch(g.exec);
         }
     ERP_CK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+    ctx->rs_capture = true;
     es = batch_enqueue(ctx, b, ratio, cfg, out, sh, matches, st);
+    ctx->rs_capture = false;
     hipGraph_t graph = nullptr;
     const hipError_t ce = hipStreamEndCapture(st, &graph);
     if (es != ERP_OK || ce != hipSuccess) {
@@ -973,8 +1083,7 @@ erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio
         ctx->graphs.erase(lru);
     }
     ctx->graphs.push_back({std::move(key), exec, ++ctx->graph_clock});
-    ERP_CK(hipGraphLaunch(exec, st));
-    return ERP_OK;
+    return launch(exec);
 }
 
 erp_status erp_match_knn2_ratio(erp_ctx* ctx, const float* d_query, int32_t nq,
@@ -1044,7 +1153,7 @@ erp_status erp_eight_point_find_dev(erp_ctx* ctx, int32_t W, int32_t H, const er
     out.hyps = d_hyps;
     erp_status es = ensure_estimator(ctx, sh, &out);
     if (es != ERP_OK) return es;
-    es = upload_w0(ctx, cfg, st);
+    es = prepare_w0(ctx, cfg, 1, st);
     if (es != ERP_OK) return es;
     ERP_CK(hipMemsetAsync(ctx->flags.p, 0, 4, st));
     ERP_CK(erp::launch_set_i32((int32_t*)ctx->counts.p, m, st));
@@ -1212,7 +1321,7 @@ erp_status erp_initial_guess(erp_ctx* ctx, const double* h_bl, const double* h_b
         erp_status es = ensure_estimator(ctx, sh, nullptr);
         if (es != ERP_OK) return es;
         if (!ensure(ctx->in_c, sizeof(erp_pair_result))) return ERP_OUT_OF_MEMORY;
-        es = upload_w0(ctx, cfg, nullptr);
+        es = prepare_w0(ctx, cfg, 1, nullptr);
         if (es != ERP_OK) return es;
         std::vector<double> pts((size_t)(m + 1) * 6, 0.0);
         for (int32_t i = 0; i < m; i++)
@@ -1302,3 +1411,151 @@ extern "C" long long erp_debug_snapshot(erp_ctx* ctx, void* host, size_t bytes) 
     }
     return (long long)ctx->snap_bytes;
 }
+
+// ================================================================ rand stream ==========
+erp_rand_stream* erp_ctx_rand_stream_internal(erp_ctx* ctx) { return ctx->rs; }  // viz.hip
+// viz.hip: random_shuffle(iota(m)) on the window `ring`, which ends up m - 1 draws further on
+void erp_shuffle_prefix_window(uint32_t ring[31], int32_t m, int32_t n, int32_t* h_idx);
+
+namespace {
+
+// the stream's (seed, draws, window) on the host, after its last device update; s->mu held
+erp_status rs_fetch(erp_rand_stream* s) {
+    if (!s->d_state) return ERP_OK;
+    ERP_CK(hipSetDevice(s->device));
+    if (s->pending) ERP_CK(hipEventSynchronize(s->ev));
+    uint32_t h[erp::kStreamNextWin];
+    ERP_CK(hipMemcpy(h, s->d_state, sizeof(h), hipMemcpyDeviceToHost));
+    memcpy(s->win, h + erp::kStreamWin, sizeof(s->win));
+    s->seed = h[erp::kStreamSeed];
+    memcpy(&s->draws, h + erp::kStreamDraws, 8);
+    return ERP_OK;
+}
+
+// set (seed, offset) or advance by n; s->mu held.  Host arithmetic before the first device use,
+// one wave on the device after it (ordered by the stream's event, on the null stream)
+erp_status rs_jump(erp_rand_stream* s, bool set, uint32_t seed, uint64_t n) {
+    if (set && seed == 0) seed = 1;
+    if (!s->d_state) {
+        if (set) {
+            host_glibc_window(seed, n, s->win);
+            s->seed = seed;
+            s->draws = n;
+        } else {
+            erp::glibc_window_jump(s->win, n);
+            s->draws += n;
+        }
+        return ERP_OK;
+    }
+    ERP_CK(hipSetDevice(s->device));
+    if (s->pending) ERP_CK(hipStreamWaitEvent(nullptr, s->ev, 0));
+    ERP_CK(erp::launch_stream_jump(s->d_state, set ? 1 : 0, seed, n, nullptr));
+    ERP_CK(hipEventRecord(s->ev, nullptr));
+    s->pending = true;
+    return ERP_OK;
+}
+
+std::mutex g_process_mu;
+std::vector<erp_rand_stream*> g_process_streams;  // by device, never freed
+
+}  // namespace
+
+extern "C" {
+
+erp_status erp_rand_stream_create(uint32_t seed, uint64_t offset, erp_rand_stream** out) {
+    if (!out) return ERP_INVALID_ARG;
+    erp_rand_stream* s = new (std::nothrow) erp_rand_stream();
+    if (!s) return ERP_OUT_OF_MEMORY;
+    (void)rs_jump(s, true, seed, offset);
+    *out = s;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_destroy(erp_rand_stream* s) {
+    if (!s || s->process_owned) return ERP_INVALID_ARG;
+    if (s->d_state) {
+        (void)hipSetDevice(s->device);
+        if (s->pending) (void)hipEventSynchronize(s->ev);
+        (void)hipEventDestroy(s->ev);
+        (void)hipFree(s->d_state);
+    }
+    delete s;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_get(erp_rand_stream* s, uint32_t* seed, uint64_t* draws) {
+    if (!s) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    const erp_status es = rs_fetch(s);
+    if (es != ERP_OK) return es;
+    if (seed) *seed = s->seed;
+    if (draws) *draws = s->draws;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_set(erp_rand_stream* s, uint32_t seed, uint64_t offset) {
+    if (!s) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    return rs_jump(s, true, seed, offset);
+}
+
+erp_status erp_rand_stream_advance(erp_rand_stream* s, uint64_t n) {
+    if (!s) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    return rs_jump(s, false, 0, n);
+}
+
+erp_status erp_rand_stream_process(int32_t device, erp_rand_stream** out) {
+    if (!out || device < 0 || device >= 1024) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(g_process_mu);
+    if (g_process_streams.size() <= (size_t)device) g_process_streams.resize((size_t)device + 1);
+    erp_rand_stream*& s = g_process_streams[(size_t)device];
+    if (!s) {
+        s = new (std::nothrow) erp_rand_stream();
+        if (!s) return ERP_OUT_OF_MEMORY;
+        (void)rs_jump(s, true, 1, 0);
+        s->device = device;
+        s->process_owned = true;
+    }
+    *out = s;
+    return ERP_OK;
+}
+
+erp_status erp_ctx_set_rand_stream(erp_ctx* ctx, erp_rand_stream* s) {
+    if (!ctx) return ERP_INVALID_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    if (s) {
+        std::lock_guard<std::mutex> g(s->mu);
+        if (s->device >= 0 && s->device != ctx->device) return ERP_INVALID_ARG;
+    }
+    ctx->rs = s;
+    return ERP_OK;
+}
+
+erp_status erp_ctx_get_rand_stream(erp_ctx* ctx, erp_rand_stream** out) {
+    if (!ctx || !out) return ERP_INVALID_ARG;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    *out = ctx->rs;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_shuffle_prefix(erp_rand_stream* s, int32_t m, int32_t n,
+                                          int32_t* h_idx) {
+    if (!s || m < 1 || n < 0 || n > m || (n > 0 && !h_idx)) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    const erp_status es = rs_fetch(s);
+    if (es != ERP_OK) return es;
+    erp_shuffle_prefix_window(s->win, m, n, h_idx);  // (steps the window m - 1 draws)
+    s->draws += (uint64_t)(m - 1);
+    if (s->d_state) {  // (rs_fetch waited for the last device update; the lock keeps others out)
+        uint32_t h[erp::kStreamNextWin];
+        memcpy(h + erp::kStreamWin, s->win, sizeof(s->win));
+        h[erp::kStreamSeed] = s->seed;
+        memcpy(h + erp::kStreamDraws, &s->draws, 8);
+        ERP_CK(hipMemcpy(s->d_state, h, sizeof(h), hipMemcpyHostToDevice));
+        s->pending = false;
+    }
+    return ERP_OK;
+}
+
+}  // extern "C"

@@ -50,6 +50,9 @@ struct BatchShape {
     // route options (erp_ctx_set_option; -1 / 0 = automatic): the sampler's block kind and split
     // replay, the Gram kernel's row tiles per wave, the throughput sampler's launch tiers
     int sampler_lat = -1, sampler_split = -1, gram_tiles = 0, sampler_tiers = -1;
+    // words between the pairs' glibc start windows (launch_sampler's w0): 0 = one window shared
+    // by every pair (cfg's seed / offset), 31 = one per pair (a rand stream, rand_stream.hip)
+    int w0_stride = 0;
 };
 
 hipError_t launch_set_i32(int32_t* p, int32_t v, hipStream_t st);  // (values via kernel args:
@@ -97,6 +100,31 @@ hipError_t launch_bearings_direct(const erp_point2f* kl, const erp_point2f* kr, 
                                   int32_t W, int32_t H, double* pts, hipStream_t st);
 hipError_t launch_jump_prep(const int32_t* counts, const BatchShape& sh, uint32_t* polyR,
                             uint32_t* polyQ, hipStream_t st);
+// ---- rand stream (rand_stream.hip): glibc rand() state that continues from call to call ----
+// host: polynomials mod P(x) = x^31 - x^28 - 1 over Z/2^32 (31 coefficients) and windows
+void glibc_poly_pow(uint64_t e, uint32_t out[31]);                   // x^e mod P, by squaring
+void glibc_poly_apply(const uint32_t c[31], uint32_t win[31]);       // win <- c(x) . win
+void glibc_window_jump(uint32_t win[31], uint64_t n);                // win <- the window n draws on
+// the sequential recurrence: the window before draw `offset` of a stream seeded with `seed`
+void glibc_window_seq(uint32_t seed, uint64_t offset, uint32_t out[31]);
+// device state of a stream, uint32 words: window [0, 31), seed [31], draws consumed [32, 34)
+// (u64), the next window [34, 65) and next draws [66, 68) between an assign and its commit
+constexpr int kStreamWin = 0, kStreamSeed = 31, kStreamDraws = 32, kStreamNextWin = 34,
+              kStreamNextDraws = 66, kStreamStateWords = 72;
+void init_stream_constants();     // the stream kernels' reduction table (once per device)
+// the current device's power table x^(k 256^j) (256 KB of device memory, built on first use):
+// blocking, so call it before a capture; false when it could not be allocated
+bool stream_tables_ready();
+// One consuming launch: pair p's start window w0s[p][31] = the window e_p draws past the
+// stream's, e_p = sum over q < p of d_q, d_q = iters (M_q - 1) for a pair the sampler runs
+// ((int)(M_q sample_frac) >= 1 and M_q >= 2) and 0 otherwise (its window is not written); then
+// the stream advances by the sum of every d_q (two kernels: assign, commit).
+hipError_t launch_stream_assign(const int32_t* counts, int n_pairs, int iters, double sample_frac,
+                                uint32_t* state, uint32_t* w0s, hipStream_t st);
+// set != 0: state <- (seed, n draws consumed); else the state advances by n draws (one wave)
+hipError_t launch_stream_jump(uint32_t* state, int set, uint32_t seed, uint64_t n,
+                              hipStream_t st);
+
 // part 0: lane end windows (jump-ahead); part 1: the backwards replay -> selection bitmaps
 hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const uint32_t* polyQ,
                           const uint32_t* w0, const BatchShape& sh, double sample_frac,

@@ -2,10 +2,14 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "../../include/erp/eight_point.hpp"
 #include "../../include/erp/feature_matcher.hpp"
+#include "../../include/erp/rand_stream.hpp"
 
 namespace erp {
 
@@ -58,6 +62,10 @@ eight_point::~eight_point() {
     if (ctx_) erp_ctx_destroy(ctx_);
 }
 
+void eight_point::use_stream(rand_stream* s) {
+    check(erp_ctx_set_rand_stream(ctx_, s ? s->handle() : nullptr), "use_stream");
+}
+
 void eight_point::find(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
                        Vec3f& R, Vec3f& T, int match_size) {
     if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
@@ -75,8 +83,10 @@ void eight_point::initial_guess(int, int, std::vector<Point3d>& l, std::vector<P
                                 Vec3f& T, int match_size) {
     if (match_size < 0 || (size_t)match_size > l.size() || (size_t)match_size > r.size())
         throw error(ERP_INVALID_ARG, "initial_guess: match_size");
-    check(erp_initial_guess(ctx_, &l[0].x, &r[0].x, match_size, &cfg, R.val, T.val, &last_),
-          "initial_guess");
+    // (no &l[0] on an empty vector)
+    const double* pl = match_size > 0 ? &l[0].x : nullptr;
+    const double* pr = match_size > 0 ? &r[0].x : nullptr;
+    check(erp_initial_guess(ctx_, pl, pr, match_size, &cfg, R.val, T.val, &last_), "initial_guess");
 }
 
 void eight_point::eight_point_estimation(int, int, std::vector<Point3d>& l, std::vector<Point3d>& r,
@@ -85,7 +95,9 @@ void eight_point::eight_point_estimation(int, int, std::vector<Point3d>& l, std:
     if (match_size < 0 || (size_t)match_size > l.size() || (size_t)match_size > r.size())
         throw error(ERP_INVALID_ARG, "eight_point_estimation: match_size");
     erp_hypothesis h;
-    check(erp_eight_point_estimation(ctx_, &l[0].x, &r[0].x, match_size, &h), "eight_point_estimation");
+    const double* pl = match_size > 0 ? &l[0].x : nullptr;
+    const double* pr = match_size > 0 ? &r[0].x : nullptr;
+    check(erp_eight_point_estimation(ctx_, pl, pr, match_size, &h), "eight_point_estimation");
     for (int k = 0; k < 3; k++) {
         R1[k] = h.R1[k];
         R2[k] = h.R2[k];
@@ -94,5 +106,36 @@ void eight_point::eight_point_estimation(int, int, std::vector<Point3d>& l, std:
     v1 = h.R1_valid != 0;
     v2 = h.R2_valid != 0;
 }
+
+rand_stream::rand_stream(uint32_t seed, uint64_t offset) {
+    check(erp_rand_stream_create(seed, offset, &s_), "rand_stream");
+}
+rand_stream::rand_stream(process_tag, int device) : owned_(false) {
+    check(erp_rand_stream_process(device, &s_), "rand_stream::process");
+}
+rand_stream::~rand_stream() {
+    if (s_ && owned_) erp_rand_stream_destroy(s_);
+}
+rand_stream& rand_stream::process(int device) {
+    static std::mutex mu;
+    static std::map<int, std::unique_ptr<rand_stream>> streams;
+    std::lock_guard<std::mutex> g(mu);
+    std::unique_ptr<rand_stream>& p = streams[device];
+    if (!p) p.reset(new rand_stream(process_tag{}, device));
+    return *p;
+}
+void rand_stream::get(uint32_t& seed, uint64_t& draws) const {
+    check(erp_rand_stream_get(s_, &seed, &draws), "rand_stream::get");
+}
+uint64_t rand_stream::draws() const {
+    uint32_t seed = 0;
+    uint64_t d = 0;
+    get(seed, d);
+    return d;
+}
+void rand_stream::set(uint32_t seed, uint64_t offset) {
+    check(erp_rand_stream_set(s_, seed, offset), "rand_stream::set");
+}
+void rand_stream::advance(uint64_t n) { check(erp_rand_stream_advance(s_, n), "rand_stream::advance"); }
 
 }  // namespace erp

@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "erp_device.hpp"
+#include "erp_jump_poly.hpp"
 #include "erp_kernels.hpp"
 #include "erp_launch.hpp"
 
@@ -91,24 +92,7 @@ __global__ void bearings_direct_kernel(const erp_point2f* __restrict__ kl,
 // 31-word window r[n..n+30] to r[n+d..n+d+30].  One wave per pair computes
 //   R_l = x^(l(M-1)) (l = 0..64) and Q_k = x^(64(M-1) 2^k),
 // the hops from a wave's first hypothesis to each lane's hypothesis and between waves.
-// One wave: out = a * b mod P (31 coefficients each, in LDS).  Lane n < 61 forms the
-// convolution coefficient c_n; lanes t < 31 then fold c_31..c_60 with the reduction table
-// column they hold in registers (cred[d] = c_red[d][t]).  out may alias neither a nor b.
-__device__ __forceinline__ void pmul_wave(const uint32_t* a, const uint32_t* b, uint32_t* out,
-                                          const uint32_t (&cred)[30]) {
-    const int lane = wave_lane();
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 31; i++) {
-        const int j = lane - i;
-        const uint32_t bj = (j >= 0 && j <= 30) ? b[j < 0 ? 0 : (j > 30 ? 30 : j)] : 0u;
-        c += a[i] * bj;
-    }
-    uint32_t r = c;
-#pragma unroll
-    for (int d = 0; d < 30; d++) r += (uint32_t)__builtin_amdgcn_readlane((int)c, 31 + d) * cred[d];
-    if (lane < 31) out[lane] = r;
-}
+// (pmul_wave, the one-wave product out = a * b mod P: erp_jump_poly.hpp)
 
 // x^(2^j) mod P, j < kPow2: the host builds it once (init_constants)
 constexpr int kPow2 = 48;  // bits of M - 1 (< 2^16) + 6 + kMaxQ (24) fit
@@ -211,13 +195,14 @@ __device__ void apply_coop(const uint32_t* __restrict__ c, uint32_t* win, uint32
 // lane end windows: win[p][w][t][lane] = r[base + (64w + lane + 1)(M-1) + t]
 __global__ __launch_bounds__(64) void sampler_window_kernel(
     const int32_t* __restrict__ counts, const uint32_t* __restrict__ polyR,
-    const uint32_t* __restrict__ polyQ, const uint32_t* __restrict__ w0, int nwaves,
-    double sample_frac, uint32_t* __restrict__ wins) {
+    const uint32_t* __restrict__ polyQ, const uint32_t* __restrict__ w0, int w0_stride,
+    int nwaves, double sample_frac, uint32_t* __restrict__ wins) {
     __shared__ uint32_t win[32], ext[64];
     const int p = blockIdx.y, w = blockIdx.x, lane = wave_lane();
     const int M = counts[p];
     if ((int)(M * sample_frac) < 1 || M < 2) return;
-    if (lane < 31) win[lane] = w0[lane];
+    // the pair's start window (w0_stride = 0: one window shared by every pair)
+    if (lane < 31) win[lane] = w0[(size_t)p * w0_stride + lane];
     __syncthreads();
     const uint32_t* Q = polyQ + (size_t)p * kMaxQ * 31;
     for (int k = 0; k < kMaxQ && (w >> k); k++)
@@ -4831,7 +4816,7 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
     const int nwaves = (sh.iters + 63) / 64;
     if (part == 0) {
         ERP_LAUNCH(sampler_window_kernel, dim3(nwaves, sh.n_pairs), dim3(64), 0, st, counts,
-                           polyR, polyQ, w0, nwaves, sample_frac, wins);
+                           polyR, polyQ, w0, sh.w0_stride, nwaves, sample_frac, wins);
     } else {
         // the lane-major bitmap (latency kernels, split replay): positions 0 .. max_s, rounded up
         // to the LDS allocation granule (1280 B = 5 words per lane on gfx950,

@@ -26,6 +26,7 @@ void* erp_ctx_stamp_buffer_internal(erp_ctx* ctx, size_t bytes, uint32_t* epoch,
 void* erp_ctx_call_begin_internal(erp_ctx* ctx, hipStream_t st);
 void erp_ctx_call_end_internal(void* call);
 void host_glibc_window(uint32_t seed, uint64_t offset, uint32_t out[31]);  // capi.hip
+erp_rand_stream* erp_ctx_rand_stream_internal(erp_ctx* ctx);               // capi.hip
 
 namespace erp {
 namespace {
@@ -281,13 +282,10 @@ struct CallGuard {
 }  // namespace
 }  // namespace erp
 
-extern "C" {
-
-erp_status erp_random_shuffle_prefix(uint32_t seed, uint64_t offset, int32_t m, int32_t n,
-                                     int32_t* h_idx) {
-    if (m < 1 || n < 0 || n > m || (n > 0 && !h_idx)) return ERP_INVALID_ARG;
-    uint32_t ring[31];
-    host_glibc_window(seed, offset, ring);
+// iota + std::random_shuffle (libstdc++: rand() % (i + 1) for i = 1 .. m-1) on the glibc window
+// `ring` (r[n-31..n-1]); the first n entries into h_idx.  On return ring is the window m - 1
+// draws further on.  (global linkage: the rand stream's shuffle in capi.hip)
+void erp_shuffle_prefix_window(uint32_t ring[31], int32_t m, int32_t n, int32_t* h_idx) {
     int pos = 0;  // ring[pos] = r[n-31]
     auto rnd = [&]() {
         const uint32_t v = ring[(pos + 28) % 31] + ring[pos];  // r[n] = r[n-3] + r[n-31]
@@ -302,6 +300,19 @@ erp_status erp_random_shuffle_prefix(uint32_t seed, uint64_t offset, int32_t m, 
         if (i != j) std::swap(idx[i], idx[j]);
     }
     for (int32_t t = 0; t < n; t++) h_idx[t] = idx[t];
+    uint32_t w[31];
+    for (int j = 0; j < 31; j++) w[j] = ring[(pos + j) % 31];
+    memcpy(ring, w, sizeof(w));
+}
+
+extern "C" {
+
+erp_status erp_random_shuffle_prefix(uint32_t seed, uint64_t offset, int32_t m, int32_t n,
+                                     int32_t* h_idx) {
+    if (m < 1 || n < 0 || n > m || (n > 0 && !h_idx)) return ERP_INVALID_ARG;
+    uint32_t ring[31];
+    host_glibc_window(seed, offset, ring);
+    erp_shuffle_prefix_window(ring, m, n, h_idx);
     return ERP_OK;
 }
 
@@ -320,7 +331,13 @@ erp_status erp_epipolar_draw_dev(erp_ctx* ctx, const erp_point2f* h_key_left,
     CallGuard call(ctx, st);
     // iota + std::random_shuffle on the glibc rand() stream (src/epipolar_tool.cpp:13-16)
     int32_t idx[kEpiMaxKeys];
-    if (n_key > 0) (void)erp_random_shuffle_prefix(seed, offset, m, n_key, idx);
+    // (a context with a rand stream draws from it, and advances it, whatever seed / offset say)
+    if (erp_rand_stream* rs = erp_ctx_rand_stream_internal(ctx)) {
+        const erp_status ss = erp_rand_stream_shuffle_prefix(rs, m, n_key, idx);
+        if (ss != ERP_OK) return ss;
+    } else if (n_key > 0) {
+        (void)erp_random_shuffle_prefix(seed, offset, m, n_key, idx);
+    }
     EpiKeys k{};
     k.n = n_key;
     static const uint8_t colors[kEpiMaxKeys][3] = {{0, 0, 255}, {0, 127, 255}, {0, 255, 255},

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../erp_match.h"
+#include "rand_stream.hpp"
 #include "types.hpp"
 
 namespace erp {
@@ -33,6 +34,12 @@ public:
     void initial_guess(int im_width, int im_height, std::vector<Point3d>& key_point_left_rect,
                        std::vector<Point3d>& key_point_right_rect, Vec3f& R_vec_out,
                        Vec3f& T_vec_out, int match_size);
+
+    // Draw from `s` and advance it, as the reference's finds share the process-global rand()
+    // (nullptr, the default: every call starts at cfg.seed / cfg.offset).  The stream must
+    // outlive this object or be detached first.  The reference's semantics in one line:
+    //   ep.use_stream(&erp::rand_stream::process());
+    void use_stream(rand_stream* s);
 
     erp_ransac_cfg cfg;                 // reference constants (erp_ransac_cfg_default)
     const erp_pair_result& last_result() const { return last_; }

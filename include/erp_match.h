@@ -184,13 +184,64 @@ int32_t erp_abi_version(void);
 erp_status erp_ctx_reserve(erp_ctx* ctx, int32_t n_pairs, int32_t max_nq, int32_t max_nt,
                            int32_t iters);
 
+/* ---- rand stream: the glibc rand() stream continued from call to call ----
+   The reference draws from glibc's process-global rand(): every eight_point::find of a process
+   goes on where the previous one stopped (one_image_test/main.cpp:135-137,
+   two_real_image_test/main.cpp:283-286; epipolar_tool.cpp:15 shuffles on the same stream).
+   Without a stream every call starts at (cfg->seed, cfg->offset), as it always did.  A rand
+   stream holds (seed, draws consumed, the 31-word glibc window); attached to a context
+   (erp_ctx_set_rand_stream) it replaces cfg->seed / cfg->offset in the CONSUMING calls:
+       erp_eight_point_find, erp_eight_point_find_dev, erp_initial_guess, erp_pair_batch_run,
+       erp_image_pairs_run (and erp_epipolar_draw_dev, which shuffles on it);
+   these ignore cfg->seed and cfg->offset, draw from the stream and advance it.  NOT consuming:
+   erp_eight_point_hypotheses_dev and the erp_consensus_* calls, which reproduce blocks of a
+   larger find at an explicit offset and stay on cfg->offset.  ERP_SAMPLER_PHILOX on a context
+   with a stream gives ERP_INVALID_ARG.
+   Consumption rule: a pair consumes iters * (M - 1) draws when the sampler runs it, that is
+   when (int)(M * sample_frac) >= 1 and M >= 2 -- whatever its final status, K == 0 included --
+   and 0 draws otherwise (the reference is undefined there: src/eight_point.cpp:101-116 with
+   sample_n == 0).  The pairs of a batch consume in pair order: pair p starts
+   iters * sum_{q<p, q consuming} (M_q - 1) draws past the stream's position at the call.  The
+   M_q stay on the device: a kernel hands every pair its start window and advances the state,
+   with no host round trip.  The counter wraps mod 2^64; the window stays the true one.
+   Order and threads: a stream may be attached to several contexts.  Calls serialise on the
+   stream (its own lock, and on the device an event recorded right after the kernel that
+   advances the state, which the next consumer on any HIP stream waits for): results follow the
+   order in which the calls take the stream, and overlapped calls on different contexts wait
+   for that kernel only, not for each other's pipelines.  Under erp_ctx_set_graphs the state
+   and the per-pair windows sit at fixed device addresses, so a replayed graph continues the
+   stream (the whole graph launch is then the stream's turn).  A stream must outlive its
+   attachment: detach (erp_ctx_set_rand_stream(ctx, NULL)) before erp_rand_stream_destroy.
+   The state lives on the host until the first GPU call uses the stream, from then on in that
+   device's memory (a stream serves one device). */
+typedef struct erp_rand_stream erp_rand_stream;
+/* host only until the first device use (works without a GPU): the stream seeded with `seed`
+   (0 = 1, as srand) after `offset` draws; positioning costs O(log offset) */
+erp_status erp_rand_stream_create(uint32_t seed, uint64_t offset, erp_rand_stream** out);
+erp_status erp_rand_stream_destroy(erp_rand_stream* s);
+/* (seed, draws consumed) after the stream's last device update (waits for it) */
+erp_status erp_rand_stream_get(erp_rand_stream* s, uint32_t* seed, uint64_t* draws);
+erp_status erp_rand_stream_set(erp_rand_stream* s, uint32_t seed, uint64_t offset);
+/* skip n draws: how a host accounts for rand() calls made elsewhere (FLANN) between calls */
+erp_status erp_rand_stream_advance(erp_rand_stream* s, uint64_t n);
+/* the process-wide stream of a device, created at (1, 0) on first request: the reference's
+   process-global state.  Never destroyed by the caller. */
+erp_status erp_rand_stream_process(int32_t device, erp_rand_stream** out);
+/* s = NULL detaches */
+erp_status erp_ctx_set_rand_stream(erp_ctx* ctx, erp_rand_stream* s);
+erp_status erp_ctx_get_rand_stream(erp_ctx* ctx, erp_rand_stream** out);
+/* erp_random_shuffle_prefix drawing from the stream: consumes m - 1 draws (0 for m < 2) */
+erp_status erp_rand_stream_shuffle_prefix(erp_rand_stream* s, int32_t m, int32_t n,
+                                          int32_t* h_idx);
+
 /* ---- stage timing (the reference's START_TIME/STOP_TIME, src/debug_print.h:9-13, applied to
    the hot path): HIP events recorded around every kernel on the pipeline's stream. ---- */
 typedef enum erp_stage {
     ERP_STAGE_KNN2_FILTER = 0,  /* bf16 split + the one MFMA pass: bounds + provisional candidates */
     ERP_STAGE_KNN2_MERGE = 1,   /* chunk fold + ratio test + compaction */
     ERP_STAGE_BEARINGS = 2,     /* gather + pixel -> bearing */
-    ERP_STAGE_JUMP_PREP = 3,    /* glibc jump-ahead polynomials */
+    ERP_STAGE_JUMP_PREP = 3,    /* glibc jump-ahead polynomials (and, on a rand stream, the
+                                   kernels that hand out the pairs' start windows) */
     ERP_STAGE_SAMPLER = 4,      /* random_array replay (glibc, backwards, bitmap) */
     ERP_STAGE_EIGEN = 5,        /* 9x9 Jacobi, rank-2 fix, decomposeEssentialMat, Euler */
     ERP_STAGE_VALID_COMPACT = 6,
