@@ -11,7 +11,8 @@ Host-side mirror of the reference's hot-path classes (Kitsunetic/ERP_match_eight
 * ``PairBatchRunner`` -- the batched hot path: match -> gather -> find for many ERP pairs,
   i.e. what src/automatic.cpp:117-126 runs per pair, as one sequence of gfx950 kernels
   (``run`` from descriptors, ``run_images`` from the ERP images via
-  ``spherical_surf.do_all_batch``).
+  ``spherical_surf.do_all_batch``, ``run_sweep`` for the drivers' rotation sweeps: one left
+  image against a right base image under a list of poses, with the surf match error).
 
 Every call goes through the C ABI of ``lib/liberp_match.so`` (include/erp_match.h); there is
 no CPU fallback.  Arrays are numpy (host, synchronous) or torch CUDA tensors (device,
@@ -30,7 +31,7 @@ from .capi import (DMATCH_DTYPE, HYP_DTYPE, RESULT_DTYPE, Context, ErpError, Ran
 __all__ = ["feature_matcher", "eight_point", "erp_rotation", "spherical_surf", "epipolar_tool",
            "PairBatchRunner", "Context", "ErpError", "RandStream", "process_rand_stream",
            "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "results_to_numpy",
-           "hyps_to_numpy", "synth", "capi"]
+           "hyps_to_numpy", "sweep_relative_rotation", "synth", "capi"]
 
 
 def _np_ptr(a: np.ndarray):
@@ -347,6 +348,36 @@ class erp_rotation:  # noqa: N801  (reference class name)
               "rotate_image")
         return out
 
+    def match_error(self, key_left, key_right, counts, rot_mats, W: int, H: int):
+        """erp_match_error_dev, the "Surf match error" of one_image_test/main.cpp:115-129: per
+        pair the mean over its matches of degree_error(rotate_pixel(key_left, rot_mat),
+        key_right), radians.  key_left / key_right: CUDA float32 [P, S, 2] (pair p's matches in
+        its first counts[p] of S slots); counts: CUDA int32 [P], any stride (e.g. the M column of
+        a batch's records); rot_mats: host [P, 3, 3] -> CUDA float64 [P], NaN where counts is 0."""
+        import torch
+        mats = _rot_mats_host(rot_mats)
+        for k in (key_left, key_right):
+            if not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.float32
+                    and k.dim() == 3 and k.shape[2] == 2 and k.is_contiguous()):
+                raise ValueError("keys are contiguous CUDA float32 tensors [P, S, 2]")
+        if not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int32
+                and counts.dim() == 1 and (counts.shape[0] < 2 or counts.stride(0) >= 1)):
+            raise ValueError("counts is a CUDA int32 tensor [P]")
+        P_, S = key_left.shape[:2]
+        if key_right.shape != key_left.shape or counts.shape[0] != P_ or mats.shape[0] != P_:
+            raise ValueError("key_left, key_right, counts and rot_mats differ in pair count")
+        if not (key_left.device == key_right.device == counts.device
+                and key_left.device.index == self.ctx.device):
+            raise ValueError(f"tensors must be on the context's device cuda:{self.ctx.device}")
+        out = torch.empty(P_, dtype=torch.float64, device=key_left.device)
+        check(self.L.erp_match_error_dev(self.ctx.h, key_left.data_ptr(), key_right.data_ptr(), S,
+                                         counts.data_ptr(),
+                                         counts.stride(0) if P_ > 1 else 1, P_, _np_ptr(mats),
+                                         int(W), int(H), out.data_ptr(),
+                                         torch.cuda.current_stream(key_left.device).cuda_stream),
+              "erp_match_error_dev")
+        return out
+
     def rot_from_vec(self, v1, v2) -> np.ndarray:
         a = np.ascontiguousarray(v1, np.float64).reshape(3)
         b = np.ascontiguousarray(v2, np.float64).reshape(3)
@@ -528,14 +559,21 @@ class spherical_surf:  # noqa: N801  (reference class name)
         n_pairs, H, W = lefts.shape[:3]
         prm = _surf_params(self.L, surf_params)
         st = torch.cuda.current_stream(lefts.device).cuda_stream
+        return self._grow_and_retry(
+            n_pairs, lefts.device, max_kp, where,
+            lambda kp, pk, info: launch(self.ctx.h, lefts.data_ptr(), rights.data_ptr(), n_pairs,
+                                        W, H, C.byref(prm), kp, fill, max_group_pairs, pk, info,
+                                        st))
+
+    def _grow_and_retry(self, n_pairs, device, max_kp, where, call):
+        """call(max_kp, byref(packed), byref(info)) -> status, repeated with a larger max_kp and
+        larger output buffers while the library reports an overflow"""
         cap_l = cap_r = 1024 * max(n_pairs, 1)
         while True:
-            buf = _PackedBuffers(n_pairs, cap_l, cap_r, lefts.device)
+            buf = _PackedBuffers(n_pairs, cap_l, cap_r, device)
             pk = buf.struct()
             info = capi.ImageBatchInfo()
-            check(launch(self.ctx.h, lefts.data_ptr(), rights.data_ptr(), n_pairs, W, H,
-                         C.byref(prm), max_kp, fill, max_group_pairs, C.byref(pk), C.byref(info),
-                         st), where)
+            check(call(max_kp, C.byref(pk), C.byref(info)), where)
             if info.fits:
                 break
             max_kp = max(max_kp, info.need_kp)
@@ -544,6 +582,32 @@ class spherical_surf:  # noqa: N801  (reference class name)
         out = buf.result(info.rows_l, info.rows_r)
         out["max_nq"], out["max_nt"] = info.max_nq, info.max_nt
         return out
+
+    def do_all_sweep(self, left, right_base, rot_mats, max_kp: int = 16384, fill: int = 0,
+                     max_group_pairs: int = 0, **surf_params):
+        """do_all up to the match for a rotation sweep (erp_image_sweep_features_dev): one left
+        image against rotate_image(right_base, inv(rot_mat)) for every pose rot_mat of rot_mats
+        (host, [P, 3, 3] float64), CUDA uint8 [H, W, 3] images -> the dict do_all_batch returns
+        for the P pairs (left repeated, right images rotated), byte for byte.  The left image's
+        features are computed once and the rotated images exist one group at a time."""
+        return self._sweep(left, right_base, rot_mats, max_kp, fill, max_group_pairs, surf_params,
+                           lambda *a: self.L.erp_image_sweep_features_dev(*a),
+                           "erp_image_sweep_features_dev")
+
+    def _sweep(self, left, right_base, rot_mats, max_kp, fill, max_group_pairs, surf_params,
+               launch, where):
+        """the grow-and-retry loop around a library call with erp_image_sweep_features_dev's
+        leading arguments (ctx .. info, stream)"""
+        import torch
+        left, right_base, mats = _sweep_inputs(left, right_base, rot_mats, self.ctx.device)
+        H, W = left.shape[:2]
+        prm = _surf_params(self.L, surf_params)
+        st = torch.cuda.current_stream(left.device).cuda_stream
+        return self._grow_and_retry(
+            mats.shape[0], left.device, max_kp, where,
+            lambda kp, pk, info: launch(self.ctx.h, left.data_ptr(), right_base.data_ptr(),
+                                        mats.shape[0], _np_ptr(mats), W, H, C.byref(prm), kp,
+                                        fill, max_group_pairs, pk, info, st))
 
     def unrotate_band_keypoints(self, key, counts, width: int, height: int):
         """do_all's keypoint step (src/spherical_surf.cpp:120-144), in place on the band
@@ -571,6 +635,66 @@ def _image_batch_dev(lefts, rights):
     if lefts.shape[1] < 4 or lefts.shape[2] < 1:
         raise ValueError("images need H >= 4 and W >= 1")
     return lefts, rights
+
+
+def _rot_mats_host(rot_mats) -> np.ndarray:
+    """poses as a contiguous host float64 array [P, 3, 3]"""
+    try:
+        import torch
+        if isinstance(rot_mats, torch.Tensor):
+            rot_mats = rot_mats.detach().cpu().numpy()
+    except ImportError:  # pragma: no cover
+        pass
+    m = np.ascontiguousarray(rot_mats, np.float64)
+    if not (m.shape[-2:] == (3, 3) and m.ndim in (2, 3)) and not (m.ndim == 2 and m.shape[1] == 9):
+        raise ValueError("rot_mats are 3x3 matrices [P, 3, 3]")
+    return m.reshape(-1, 3, 3)
+
+
+def _sweep_inputs(left, right_base, rot_mats, device: int):
+    """the images and poses of do_all_sweep / run_sweep, checked before any call"""
+    left, right_base = _img_dev(left), _img_dev(right_base)
+    if left.shape != right_base.shape or left.device != right_base.device:
+        raise ValueError("left and right_base differ in shape or device")
+    if left.device.index != device:
+        raise ValueError(f"images must be on the context's device cuda:{device}")
+    if left.shape[0] < 4 or left.shape[1] < 1:
+        raise ValueError("images need H >= 4 and W >= 1")
+    return left, right_base, _rot_mats_host(rot_mats)
+
+
+def sweep_relative_rotation(results, initial_rot_mat) -> np.ndarray:
+    """two_real_image_test/main.cpp:215-219 for a sweep's records, host only:
+    result_rot_vec = rot2eular(eular2rot((double)R) * initial_rot_mat.inv()) per pose ->
+    [P, 3] float64 (radians).  results: run_sweep's ``results`` (tensor or RESULT_DTYPE array)
+    or the R vectors [P, 3]."""
+    L = capi.load()
+    try:
+        import torch
+        if isinstance(results, torch.Tensor):
+            results = (results_to_numpy(results) if results.dtype == torch.uint8
+                       else results.detach().cpu().numpy())
+    except ImportError:  # pragma: no cover
+        pass
+    r = np.asarray(results)
+    if r.dtype.names:
+        r = r["R"]
+    r = np.ascontiguousarray(r, np.float32).reshape(-1, 3).astype(np.float64)  # Vec3f -> Vec3d
+    init = _m9(initial_rot_mat)
+    inv = np.zeros(9, np.float64)
+    if not L.erp_inv3(_np_ptr(init), _np_ptr(inv)):
+        raise ErpError(capi.ERP_INVALID_ARG, "sweep_relative_rotation: singular initial_rot_mat")
+    b = inv.reshape(3, 3)
+    out = np.zeros((r.shape[0], 3), np.float64)
+    a, prod = np.zeros(9, np.float64), np.zeros(9, np.float64)
+    for p in range(r.shape[0]):
+        L.erp_eular2rot(_np_ptr(np.ascontiguousarray(r[p])), _np_ptr(a))
+        m = a.reshape(3, 3)
+        for i in range(3):      # cv::gemm on 3x3 doubles: (a0 b0 + a1 b1) + a2 b2
+            for j in range(3):
+                prod[i * 3 + j] = (m[i, 0] * b[0, j] + m[i, 1] * b[1, j]) + m[i, 2] * b[2, j]
+        L.erp_rot2eular(_np_ptr(prod), _np_ptr(out[p]))
+    return out
 
 
 def _surf_params(L, params):
@@ -710,6 +834,65 @@ class PairBatchRunner:
                                            surf_params, launch, "erp_image_pairs_run")
         self.last_info = ss.last_info
         return {"results": res[:n_pairs]}
+
+    def run_sweep(self, left, right_base, rot_mats, ratio: float = 0.3, want=(),
+                  match_error: bool = True, chunk: int = 128, max_kp: int = 16384, fill: int = 0,
+                  max_group_pairs: int = 0, **surf_params):
+        """The reference drivers' rotation sweep (one_image_test/main.cpp:73-145 and the two
+        16^3 drivers): one left image against rotate_image(right_base, inv(rot_mat)) for every
+        pose of rot_mats (host [P, 3, 3]) -> {"results": records [P], "match_error": CUDA
+        float64 [P] (the drivers' "Surf match error", radians; match_error=False leaves it
+        out), ...}.  The left image's features are computed once per library call and the poses
+        go through in chunks of ``chunk`` per call (erp_image_sweep_run), so the rotated images
+        and the packed buffers stay bounded whatever P; with a RandStream attached the poses
+        draw from it one after the other.  Optional outputs (``want``, as run()) need
+        P <= chunk -- their shapes depend on the chunk's max_nq -- and take the route
+        do_all_sweep -> run() -> erp_rotation.match_error.  ``last_packed`` / ``last_info``
+        keep the last chunk's packed batch and info."""
+        import torch
+        left, right_base, mats = _sweep_inputs(left, right_base, rot_mats, self.ctx.device)
+        n, chunk = mats.shape[0], int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        if want and n > chunk:
+            raise ValueError("optional outputs need every pose in one chunk (P <= chunk)")
+        H, W = left.shape[:2]
+        dev = left.device
+        ss = spherical_surf(ctx=self.ctx)
+        if want and n:
+            p = ss.do_all_sweep(left, right_base, mats, max_kp=max_kp, fill=fill,
+                                max_group_pairs=max_group_pairs, **surf_params)
+            self.last_packed, self.last_info = p, ss.last_info
+            keys = ("key_left", "key_right") if match_error else ()
+            outs = self.run(*[p[k] for k in ("desc_l", "desc_r", "kp_l", "kp_r", "off_l", "off_r",
+                                             "width", "height", "max_nq", "max_nt")],
+                            ratio=ratio, want=tuple(want) + tuple(k for k in keys if k not in want))
+            res = {k: v for k, v in outs.items() if k == "results" or k in want}
+            if match_error:
+                m_col = outs["results"].view(torch.int32)[:, RESULT_DTYPE.fields["M"][1] // 4]
+                res["match_error"] = erp_rotation(ctx=self.ctx).match_error(
+                    outs["key_left"], outs["key_right"], m_col, mats, W, H)
+            return res
+        res = torch.empty((max(n, 1), RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        err = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        for c0 in range(0, n, chunk):
+            c1 = min(n, c0 + chunk)
+
+            def launch(h, l_ptr, r_ptr, n_poses, m_ptr, W_, H_, prm, kp, fl, grp, pk, info, st):
+                o = capi.BatchOutputs(res[c0:].data_ptr())
+                return self.ctx.L.erp_image_sweep_run(
+                    h, l_ptr, r_ptr, n_poses, m_ptr, W_, H_, prm, kp, fl, grp, pk, ratio,
+                    C.byref(self.cfg), C.byref(o), err[c0:].data_ptr() if match_error else None,
+                    info, st)
+            self.last_packed = ss._sweep(left, right_base, mats[c0:c1], max_kp, fill,
+                                         max_group_pairs, surf_params, launch,
+                                         "erp_image_sweep_run")
+            self.last_info = ss.last_info
+            max_kp = max(max_kp, self.last_info["need_kp"])  # the next chunk starts where this fit
+        out = {"results": res[:n]}
+        if match_error:
+            out["match_error"] = err[:n]
+        return out
 
     def _launch(self, b, ratio, outs, stream, dev):
         import torch

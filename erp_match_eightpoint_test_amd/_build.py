@@ -19,10 +19,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ERP_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip", "surf.hip", "surf_api.hip", "viz.hip",
-           "image_batch.hip", "rand_stream.hip",
+           "image_batch.hip", "rand_stream.hip", "sweep.hip",
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
-           "erp_launch.hpp", "erp_jump_poly.hpp"]
+           "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp"]
 PUBLIC_HEADERS = ["erp_match.h", os.path.join("erp", "feature_matcher.hpp"),
                   os.path.join("erp", "eight_point.hpp"), os.path.join("erp", "rand_stream.hpp")]
 

@@ -100,7 +100,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_rand_stream_create", "erp_rand_stream_destroy", "erp_rand_stream_get",
             "erp_rand_stream_set", "erp_rand_stream_advance", "erp_rand_stream_process",
             "erp_ctx_set_rand_stream", "erp_ctx_get_rand_stream",
-            "erp_rand_stream_shuffle_prefix"]
+            "erp_rand_stream_shuffle_prefix", "erp_image_sweep_features_dev",
+            "erp_image_sweep_run", "erp_match_error_dev"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -238,6 +239,16 @@ def load(build_if_missing: bool = False):
                                       C.POINTER(SurfParams), C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(PackedPairs), C.c_float, C.POINTER(RansacCfg),
                                       C.POINTER(BatchOutputs), C.POINTER(ImageBatchInfo), P]
+    L.erp_image_sweep_features_dev.argtypes = [P, P, P, C.c_int32, P, C.c_int32, C.c_int32,
+                                               C.POINTER(SurfParams), C.c_int32, C.c_int32,
+                                               C.c_int32, C.POINTER(PackedPairs),
+                                               C.POINTER(ImageBatchInfo), P]
+    L.erp_image_sweep_run.argtypes = [P, P, P, C.c_int32, P, C.c_int32, C.c_int32,
+                                      C.POINTER(SurfParams), C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(PackedPairs), C.c_float, C.POINTER(RansacCfg),
+                                      C.POINTER(BatchOutputs), P, C.POINTER(ImageBatchInfo), P]
+    L.erp_match_error_dev.argtypes = [P, P, P, C.c_int64, P, C.c_int64, C.c_int32, P, C.c_int32,
+                                      C.c_int32, P, P]
     L.erp_rand_stream_create.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(P)]
     L.erp_rand_stream_destroy.argtypes = [P]
     L.erp_rand_stream_get.argtypes = [P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]

@@ -132,7 +132,8 @@ struct erp_ctx {
     // graph launch: an event inside a captured region orders nothing outside it)
     erp_rand_stream* rs = nullptr;
     bool rs_capture = false;
-    DevBuf extra[18];         // erp_ctx_scratch_internal slots (1-11 SURF, 12 viz, 13-17 image batch)
+    DevBuf extra[24];         // erp_ctx_scratch_internal slots (1-11 SURF, 12 viz, 13-17 image
+                              // batch, 18-23 sweep: erp_image_batch.hpp)
     // route options (erp_ctx_set_option; include/erp_match.h documents each, defaults below)
     int32_t opt[ERP_OPT_COUNT] = {
         -1,  // SMALL_BATCH: auto

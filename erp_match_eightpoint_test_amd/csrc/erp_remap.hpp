@@ -86,5 +86,10 @@ void pitch_matrix(float deg, double m[9]);
 erp_status spherical_bands_enqueue(erp_ctx* ctx, const uint8_t* d_ims, int32_t n_images,
                                    int32_t W, int32_t H, uint8_t* d_bands,
                                    size_t band_set_stride, hipStream_t st);
+// rotate_image of ONE image by n matrices (m [n][9]: what rotate_pixel applies, i.e. the
+// inverse of rotate_image's argument) into n contiguous H x W x 3 outputs, kMaxRemapJobs FULL
+// jobs per launch; no argument checks, the caller holds the context's call section
+erp_status rotate_images_enqueue(erp_ctx* ctx, const uint8_t* d_im, int32_t n, const double* m,
+                                 int32_t W, int32_t H, uint8_t* d_out, hipStream_t st);
 
 }  // namespace erp

@@ -21,6 +21,7 @@
 
 #include "../../include/erp_match.h"
 #include "erp_device.hpp"
+#include "erp_image_batch.hpp"
 #include "erp_launch.hpp"
 #include "erp_remap.hpp"
 #include "erp_surf.hpp"
@@ -38,33 +39,23 @@ struct CtxCallGuard {
     ~CtxCallGuard() { erp_ctx_call_end_internal(h); }
 };
 
-// The automatic group size (the one place it comes from; DESIGN.md section 3.8 has the A/B):
-// the largest group whose SURF scratch + band canvases + staging stay within the budget, and
-// no more than kMaxAutoGroupPairs pairs.  9 GiB holds 8 pairs of 5376 x 2688 (1.08 GB each),
-// the fastest of 4 / 8 / 16 there; at 1344 x 672, where the budget would allow ~58 pairs, groups
-// of 8 ran 64 pairs 1.5x faster than one group of 64 (SURF's per-band cost grows with the
-// bands per call), hence the cap.
-constexpr size_t kGroupBudgetBytes = (size_t)9 << 30;
-constexpr int32_t kMaxAutoGroupPairs = 8;
-
-// context scratch slots (capi.hip erp_ctx::extra)
-enum { kSlotBands = 13, kSlotKp = 14, kSlotDesc = 15, kSlotCount = 16, kSlotRowBase = 17 };
-
 constexpr int kPackRowsPerBlock = 16;  // 256 threads = 16 rows x 16 lanes of 16 B
 constexpr int kPackMaxBlocksPerBand = 16;
 
 struct PackArgs {
     double m[4][9];      // per band: rotate_keypoint's matrix (band 1 unused: the shift band)
     erp_packed_pairs o;
-    const erp_keypoint* kp;
-    const float* desc;
-    const int32_t* count;
+    erp::PackSide s[2];  // where each side's band images are (left, right)
     int64_t* row_base;   // [8 n_pairs] first output row of every band (scratch)
     int32_t n_pairs, max_kp, pair0, W, H;
 };
 
 __device__ __forceinline__ int32_t clamp_count(int32_t c, int32_t max_kp) {
     return min(max(c, 0), max_kp);
+}
+// the band image holding band `band` of pair p's side
+__device__ __forceinline__ size_t src_image(const erp::PackSide& s, int p, int band) {
+    return (size_t)s.first + (size_t)p * s.pair_stride + band;
 }
 
 // One block: the group's pair offsets (appended after out.off_*[pair0], which the previous
@@ -89,7 +80,9 @@ __global__ __launch_bounds__(256) void pack_offsets_kernel(PackArgs a) {
         int64_t nl = 0, nr = 0;
 #pragma unroll
         for (int k = 0; k < 8; k++) {
-            c[k] = p < a.n_pairs ? clamp_count(a.count[(size_t)p * 8 + k], a.max_kp) : 0;
+            c[k] = p < a.n_pairs
+                       ? clamp_count(a.s[k >> 2].count[src_image(a.s[k >> 2], p, k & 3)], a.max_kp)
+                       : 0;
             if (k < 4) nl += c[k];
             else nr += c[k];
         }
@@ -132,18 +125,20 @@ __global__ __launch_bounds__(256) void pack_offsets_kernel(PackArgs a) {
     }
 }
 
-// blockIdx.x = band image ([pair][side][band]), blockIdx.y strides over its rows.  Rows at or
+// blockIdx.x = output band ([pair][side][band]; its rows come from the band image the side's
+// PackSide maps it to), blockIdx.y strides over its rows.  Rows at or
 // past the band's count are not read; rows at or past the side's capacity are not written.
 __global__ __launch_bounds__(256) void pack_rows_kernel(PackArgs a) {
-    const size_t img = blockIdx.x;
-    const int side = (int)(img >> 2) & 1, band = (int)img & 3;
-    const int32_t n = clamp_count(a.count[img], a.max_kp);
+    const int side = (int)(blockIdx.x >> 2) & 1, band = (int)blockIdx.x & 3;
+    const erp::PackSide& s = a.s[side];
+    const size_t img = src_image(s, (int)(blockIdx.x >> 3), band);
+    const int32_t n = clamp_count(s.count[img], a.max_kp);
     if (n == 0) return;
-    const int64_t base = a.row_base[img];
+    const int64_t base = a.row_base[blockIdx.x];
     const int64_t cap = side ? a.o.cap_r : a.o.cap_l;
     const int tid = threadIdx.x;
     // descriptors: consecutive lanes on consecutive 16-byte pieces of a 256-byte row
-    const float4* __restrict__ src = (const float4*)a.desc + img * (size_t)a.max_kp * 16;
+    const float4* __restrict__ src = (const float4*)s.desc + img * (size_t)a.max_kp * 16;
     float4* __restrict__ dst = (float4*)(side ? a.o.desc_r : a.o.desc_l);
     const int lane = tid & 15;
     for (int r = blockIdx.y * kPackRowsPerBlock + (tid >> 4); r < n;
@@ -153,7 +148,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(PackArgs a) {
         dst[(size_t)row * 16 + lane] = src[(size_t)r * 16 + lane];
     }
     // keypoints: pt of the cv::KeyPoint records -> un-rotated ERP pixels
-    const erp_keypoint* __restrict__ ksrc = a.kp + img * (size_t)a.max_kp;
+    const erp_keypoint* __restrict__ ksrc = s.kp + img * (size_t)a.max_kp;
     erp_point2f* __restrict__ kdst = side ? a.o.kp_r : a.o.kp_l;
     for (int r = blockIdx.y * 256 + tid; r < n; r += gridDim.y * 256) {
         const int64_t row = base + r;
@@ -165,7 +160,11 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(PackArgs a) {
     }
 }
 
-bool dims_ok(int32_t W, int32_t H) {
+}  // namespace
+
+namespace erp {
+
+bool image_dims_ok(int32_t W, int32_t H) {
     return W > 0 && H >= 4 && (int64_t)W * H <= ((int64_t)1 << 31) / 3;
 }
 
@@ -175,19 +174,16 @@ bool packed_ok(const erp_packed_pairs* o) {
            ((uintptr_t)o->desc_l & 15) == 0 && ((uintptr_t)o->desc_r & 15) == 0;
 }
 
-// the two pack launches for pairs [pair0, pair0 + n_pairs) of a call (the caller holds the
-// context's call section); d_kp / d_desc / d_count describe these pairs only
-erp_status pack_enqueue(erp_ctx* ctx, const erp_keypoint* d_kp, const float* d_desc,
-                        const int32_t* d_count, int32_t n_pairs, int32_t max_kp, int32_t pair0,
-                        int32_t W, int32_t H, const erp_packed_pairs& out, hipStream_t st) {
+erp_status pack_enqueue(erp_ctx* ctx, const PackSide side[2], int32_t n_pairs, int32_t max_kp,
+                        int32_t pair0, int32_t W, int32_t H, const erp_packed_pairs& out,
+                        hipStream_t st) {
     static const float pitch[4] = {45.f, 0.f, -45.f, -90.f};  // do_all :121-126
     PackArgs a{};
     for (int b = 0; b < 4; b++)
         if (b != 1) erp::pitch_matrix(pitch[b], a.m[b]);
     a.o = out;
-    a.kp = d_kp;
-    a.desc = d_desc;
-    a.count = d_count;
+    a.s[0] = side[0];
+    a.s[1] = side[1];
     a.row_base = (int64_t*)erp_ctx_scratch_internal(ctx, kSlotRowBase,
                                                     (size_t)n_pairs * 8 * sizeof(int64_t));
     if (!a.row_base) return ERP_OUT_OF_MEMORY;
@@ -203,6 +199,69 @@ erp_status pack_enqueue(erp_ctx* ctx, const erp_keypoint* d_kp, const float* d_d
     return hipGetLastError() == hipSuccess ? ERP_OK : ERP_HIP_ERROR;
 }
 
+erp_status packed_totals(const erp_packed_pairs& out, int32_t n_pairs, int32_t max_kp,
+                         int32_t raw_max, erp_image_batch_info* info, hipStream_t st) {
+    std::vector<int64_t> off(2 * ((size_t)n_pairs + 1));
+    const size_t ob = ((size_t)n_pairs + 1) * sizeof(int64_t);
+    if (hipMemcpyAsync(off.data(), out.off_l, ob, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(off.data() + n_pairs + 1, out.off_r, ob, hipMemcpyDeviceToHost, st) !=
+            hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return ERP_HIP_ERROR;
+    const int64_t* ol = off.data();
+    const int64_t* orr = off.data() + n_pairs + 1;
+    int64_t mq = 0, mt = 0;
+    for (int32_t p = 0; p < n_pairs; p++) {
+        mq = std::max(mq, ol[p + 1] - ol[p]);
+        mt = std::max(mt, orr[p + 1] - orr[p]);
+    }
+    info->need_kp = raw_max;
+    info->max_nq = (int32_t)mq;  // <= 4 max_kp
+    info->max_nt = (int32_t)mt;
+    info->rows_l = ol[n_pairs];
+    info->rows_r = orr[n_pairs];
+    info->fits = raw_max <= max_kp && info->rows_l <= out.cap_l && info->rows_r <= out.cap_r;
+    return ERP_OK;
+}
+
+erp_status packed_batch_run(erp_ctx* ctx, const erp_packed_pairs& packed, int32_t n_pairs,
+                            const erp_image_batch_info& info, float ratio,
+                            const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
+                            hipStream_t st) {
+    erp_pair_batch b{};
+    b.n_pairs = n_pairs;
+    b.dim = 64;
+    b.max_nq = info.max_nq;
+    b.max_nt = info.max_nt;
+    b.desc_l = packed.desc_l;
+    b.desc_r = packed.desc_r;
+    b.kp_l = packed.kp_l;
+    b.kp_r = packed.kp_r;
+    b.off_l = packed.off_l;
+    b.off_r = packed.off_r;
+    b.width = packed.width;
+    b.height = packed.height;
+    return erp_pair_batch_run(ctx, &b, ratio, cfg, out, (void*)st);
+}
+
+}  // namespace erp
+
+namespace {
+
+using erp::kSlotBands;
+using erp::kSlotCount;
+using erp::kSlotDesc;
+using erp::kSlotKp;
+
+// both sides of pairs whose band images lie [pair][left, right][n0..n3] in one array
+erp_status pack_pairs_enqueue(erp_ctx* ctx, const erp_keypoint* d_kp, const float* d_desc,
+                              const int32_t* d_count, int32_t n_pairs, int32_t max_kp,
+                              int32_t pair0, int32_t W, int32_t H, const erp_packed_pairs& out,
+                              hipStream_t st) {
+    const erp::PackSide side[2] = {{d_kp, d_desc, d_count, 8, 0}, {d_kp, d_desc, d_count, 8, 4}};
+    return erp::pack_enqueue(ctx, side, n_pairs, max_kp, pair0, W, H, out, st);
+}
+
 erp_status features_checked(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
                             int32_t n_pairs, int32_t W, int32_t H, const erp_surf_params* prm,
                             int32_t max_kp, int32_t fill, int32_t max_group_pairs,
@@ -210,9 +269,9 @@ erp_status features_checked(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* 
                             hipStream_t st) {
     if (!ctx || !info) return ERP_INVALID_ARG;
     *info = erp_image_batch_info{};
-    if (n_pairs < 0 || n_pairs > (1 << 24) || !dims_ok(W, H) ||
+    if (n_pairs < 0 || n_pairs > (1 << 24) || !erp::image_dims_ok(W, H) ||
         !erp::surf_args_ok(W, H / 4, 3, prm, max_kp) || fill < 0 || fill > 255 ||
-        max_group_pairs < 0 || !packed_ok(out) || (n_pairs > 0 && (!d_left || !d_right)))
+        max_group_pairs < 0 || !erp::packed_ok(out) || (n_pairs > 0 && (!d_left || !d_right)))
         return ERP_INVALID_ARG;
     if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
     CtxCallGuard call(ctx, st);
@@ -231,8 +290,9 @@ erp_status features_checked(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* 
                                  K * (sizeof(erp_keypoint) + 64 * 4) + sizeof(int32_t));
     int32_t g = max_group_pairs > 0
                     ? max_group_pairs
-                    : (int32_t)std::min<size_t>(std::max<size_t>(kGroupBudgetBytes / per_pair, 1),
-                                                (size_t)kMaxAutoGroupPairs);
+                    : (int32_t)std::min<size_t>(
+                          std::max<size_t>(erp::kGroupBudgetBytes / per_pair, 1),
+                          (size_t)erp::kMaxAutoGroupPairs);
     g = std::min(g, n_pairs);
     uint8_t* bands = (uint8_t*)erp_ctx_scratch_internal(ctx, kSlotBands, (size_t)g * 8 * band);
     erp_keypoint* kp = (erp_keypoint*)erp_ctx_scratch_internal(
@@ -255,32 +315,13 @@ erp_status features_checked(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* 
         if (s == ERP_OK)
             s = erp::surf_detect_compute_enqueue(ctx, bands, gp * 8, W, Hb, 3, prm, max_kp, kp,
                                                  desc, cnt, st, &raw_max);
-        if (s == ERP_OK) s = pack_enqueue(ctx, kp, desc, cnt, gp, max_kp, p0, W, H, *out, st);
+        if (s == ERP_OK)
+            s = pack_pairs_enqueue(ctx, kp, desc, cnt, gp, max_kp, p0, W, H, *out, st);
         if (s != ERP_OK) return s;
         info->groups++;
     }
     // the totals for the caller: one copy + sync per call
-    std::vector<int64_t> off(2 * ((size_t)n_pairs + 1));
-    const size_t ob = ((size_t)n_pairs + 1) * sizeof(int64_t);
-    if (hipMemcpyAsync(off.data(), out->off_l, ob, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(off.data() + n_pairs + 1, out->off_r, ob, hipMemcpyDeviceToHost, st) !=
-            hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return ERP_HIP_ERROR;
-    const int64_t* ol = off.data();
-    const int64_t* orr = off.data() + n_pairs + 1;
-    int64_t mq = 0, mt = 0;
-    for (int32_t p = 0; p < n_pairs; p++) {
-        mq = std::max(mq, ol[p + 1] - ol[p]);
-        mt = std::max(mt, orr[p + 1] - orr[p]);
-    }
-    info->need_kp = raw_max;
-    info->max_nq = (int32_t)mq;  // <= 4 max_kp
-    info->max_nt = (int32_t)mt;
-    info->rows_l = ol[n_pairs];
-    info->rows_r = orr[n_pairs];
-    info->fits = raw_max <= max_kp && info->rows_l <= out->cap_l && info->rows_r <= out->cap_r;
-    return ERP_OK;
+    return erp::packed_totals(*out, n_pairs, max_kp, raw_max, info, st);
 }
 
 }  // namespace
@@ -291,8 +332,8 @@ erp_status erp_pack_band_features_dev(erp_ctx* ctx, const erp_keypoint* d_kp, co
                                       const int32_t* d_count, int32_t n_pairs, int32_t max_kp,
                                       int32_t W, int32_t H, const erp_packed_pairs* out,
                                       void* stream) {
-    if (!ctx || n_pairs < 0 || n_pairs > (1 << 24) || max_kp < 1 || !dims_ok(W, H) ||
-        !packed_ok(out) || (n_pairs > 0 && (!d_kp || !d_desc || !d_count)) ||
+    if (!ctx || n_pairs < 0 || n_pairs > (1 << 24) || max_kp < 1 || !erp::image_dims_ok(W, H) ||
+        !erp::packed_ok(out) || (n_pairs > 0 && (!d_kp || !d_desc || !d_count)) ||
         ((uintptr_t)d_desc & 15) != 0)
         return ERP_INVALID_ARG;
     if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
@@ -303,7 +344,7 @@ erp_status erp_pack_band_features_dev(erp_ctx* ctx, const erp_keypoint* d_kp, co
                        hipMemsetAsync(out->off_r, 0, sizeof(int64_t), st) == hipSuccess
                    ? ERP_OK
                    : ERP_HIP_ERROR;
-    return pack_enqueue(ctx, d_kp, d_desc, d_count, n_pairs, max_kp, 0, W, H, *out, st);
+    return pack_pairs_enqueue(ctx, d_kp, d_desc, d_count, n_pairs, max_kp, 0, W, H, *out, st);
 }
 
 erp_status erp_image_pairs_features_dev(erp_ctx* ctx, const uint8_t* d_left,
@@ -329,20 +370,9 @@ erp_status erp_image_pairs_run(erp_ctx* ctx, const uint8_t* d_left, const uint8_
                                           fill, max_group_pairs, packed, info,
                                           (hipStream_t)stream);
     if (s != ERP_OK || !info->fits || n_pairs == 0) return s;
-    erp_pair_batch b{};
-    b.n_pairs = n_pairs;
-    b.dim = 64;
-    b.max_nq = info->max_nq;
-    b.max_nt = info->max_nt;
-    b.desc_l = packed->desc_l;
-    b.desc_r = packed->desc_r;
-    b.kp_l = packed->kp_l;
-    b.kp_r = packed->kp_r;
-    b.off_l = packed->off_l;
-    b.off_r = packed->off_r;
-    b.width = packed->width;
-    b.height = packed->height;
-    return erp_pair_batch_run(ctx, &b, ratio, cfg, out, stream);
+    return erp::packed_batch_run(ctx, *packed, n_pairs, *info, ratio, cfg, out,
+                                 (hipStream_t)stream);
 }
 
 }  // extern "C"
+

@@ -101,6 +101,28 @@ erp_status spherical_bands_enqueue(erp_ctx* ctx, const uint8_t* d_ims, int32_t n
     }
     return ERP_OK;
 }
+
+erp_status rotate_images_enqueue(erp_ctx* ctx, const uint8_t* d_im, int32_t n, const double* m,
+                                 int32_t W, int32_t H, uint8_t* d_out, hipStream_t st) {
+    erp::RemapScratch scr;
+    if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
+    const size_t img = (size_t)W * H * 3;
+    for (int i0 = 0; i0 < n; i0 += erp::kMaxRemapJobs) {
+        erp::RemapJobs jobs{};
+        const int nj = std::min(n - i0, (int)erp::kMaxRemapJobs);
+        for (int k = 0; k < nj; k++) {
+            erp::RemapJob& j = jobs.j[k];
+            j.src = d_im;
+            j.dst = d_out + (size_t)(i0 + k) * img;
+            memcpy(j.m, m + (size_t)(i0 + k) * 9, sizeof(j.m));
+            j.row0 = 0;
+            j.rows = H;
+            j.mode = erp::kRemapFull;
+        }
+        if (erp::launch_remap(jobs, nj, H, W, W, H, scr, st) != hipSuccess) return ERP_HIP_ERROR;
+    }
+    return ERP_OK;
+}
 }  // namespace erp
 
 extern "C" {

@@ -553,6 +553,73 @@ erp_status erp_image_pairs_run(erp_ctx* ctx, const uint8_t* d_left, const uint8_
                                const erp_batch_outputs* out, erp_image_batch_info* info,
                                void* stream);
 
+/* ---- rotation sweep: one left image against one right base image under a list of poses ----
+   What the reference's experiment drivers run per pose (one_image_test/main.cpp:73-145,
+   two_synthesis_image_test/main.cpp:80-141, two_real_image_test/main.cpp:169-230):
+       rot_mat = eular2rot(rot_vec);  im2 = rotate_image(im_right, rot_mat.inv());
+       do_all(im_left, im2, ...);  [the match error];  eight_point::find(...)
+   for n_poses poses in one call.  A pose is the driver's rot_mat: h_rot_mat [n_poses][9],
+   row-major 3x3 doubles on the HOST, as erp_eular2rot gives them (read before the call
+   returns).  Per pose the library forms rot_mat_inv = erp_inv3(rot_mat) and rotates the right
+   base image as erp_rotate_image_dev(.., rot_mat_inv, ..) does, so the matrix the remap applies
+   is inv3(inv3(rot_mat)) (rotate_image inverts its argument, src/erp_rotation.cpp:103).  A pose
+   either inversion finds singular gives ERP_INVALID_ARG before any GPU work.
+   The left image's bands and SURF are computed once per call, and only one group's rotated
+   right images exist at a time (in context scratch), so the pose count is bounded by the
+   packed outputs alone. */
+/* The features stage.  d_left, d_right_base: one H x W x 3 image each.  The result is the packed
+   batch erp_image_pairs_features_dev writes for n_poses pairs whose left image is d_left and
+   whose right image p is rotate_image(right_base, inv3(rot_mat[p])) on a canvas pre-filled with
+   `fill` -- byte for byte, *info included (groups apart: it counts this call's groups of
+   poses).  Every pair's left rows are the left image's: off_l[p] = p * n_left, band_counts[p][0]
+   the left counts; need_kp covers the left bands too.  max_kp, fill (canvases of the rotated
+   images and of the bands), max_group_pairs (poses per group, 0 = the largest that fits the
+   budget, at most 8), the overflow convention (info->fits with ERP_OK) and the limits -- not
+   graph-capturable, synchronises `stream` a fixed few times per group -- are
+   erp_image_pairs_features_dev's. */
+erp_status erp_image_sweep_features_dev(erp_ctx* ctx, const uint8_t* d_left,
+                                        const uint8_t* d_right_base, int32_t n_poses,
+                                        const double* h_rot_mat, int32_t W, int32_t H,
+                                        const erp_surf_params* params, int32_t max_kp,
+                                        int32_t fill, int32_t max_group_pairs,
+                                        const erp_packed_pairs* out, erp_image_batch_info* info,
+                                        void* stream);
+/* erp_image_sweep_features_dev followed, when info->fits and n_poses > 0, by erp_pair_batch_run
+   on the packed batch (as erp_image_pairs_run) and, when d_match_error != NULL, by the match
+   error of every pose into d_match_error [n_poses] (device).  With a rand stream attached to
+   the context the poses draw from it one after the other, as erp_pair_batch_run's pairs do.
+   The matched keypoints the match error reads go to out->key_left / key_right where the caller
+   gave them (they keep their meaning: [n_poses][info->max_nq]) and to context scratch where
+   not.  When info->fits is 0 nothing past the features stage ran (ERP_OK: rerun larger). */
+erp_status erp_image_sweep_run(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right_base,
+                               int32_t n_poses, const double* h_rot_mat, int32_t W, int32_t H,
+                               const erp_surf_params* params, int32_t max_kp, int32_t fill,
+                               int32_t max_group_pairs, const erp_packed_pairs* packed,
+                               float ratio, const erp_ransac_cfg* cfg,
+                               const erp_batch_outputs* out, double* d_match_error,
+                               erp_image_batch_info* info, void* stream);
+/* The match error alone (one_image_test/main.cpp:115-129 with degree_error :27-50), device
+   keypoints, asynchronous on `stream`.  Pair p's matches are d_key_left / d_key_right
+   [p * key_stride + i], i < M_p = d_m[p * m_stride] (m_stride in int32 units, >= 1, so
+   &results[0].M with sizeof(erp_pair_result) / 4 reads a batch's records; a negative count is
+   0, one above key_stride is key_stride); h_rot_mat [n_pairs][9] on the host is each pair's
+   pose rot_mat -- applied itself, not its inverse.  Per match, in double:
+       (r, c)  = rotate_pixel((int)key_left.y, (int)key_left.x, rot_mat)   (x86 truncation)
+       v1      = Point2f((float)c, (float)r),  v2 = key_right
+       angles  = M_PI * y / H,  2 * M_PI * x / W      (the float coordinate widened)
+       vec     = (sin a cos b, sin a sin b, cos a)    (:35-41, not OMAF's signs)
+       product = v1[0] v2[0] + v1[1] v2[1] + v1[2] v2[2]   (left to right, no FMA)
+       error   = product < 1 ? acos(product) : 0
+   d_out[p] = (the errors added one after the other in match order, from 0.0) / M_p in radians
+   (the driver prints it as "degree"); NaN for M_p = 0, as the reference's 0.0 / 0.  The order
+   of the sum is fixed, so the result is bit-identical from run to run; sin / cos / acos are
+   the device library's (a few ulp from glibc's: <= 1e-7 rad on the mean). */
+erp_status erp_match_error_dev(erp_ctx* ctx, const erp_point2f* d_key_left,
+                               const erp_point2f* d_key_right, int64_t key_stride,
+                               const int32_t* d_m, int64_t m_stride, int32_t n_pairs,
+                               const double* h_rot_mat, int32_t W, int32_t H, double* d_out,
+                               void* stream);
+
 /* ---- visual outputs, device images ---- */
 /* epipolar_tool (src/epipolar_tool.hpp / .cpp:7-71, constructor + draw_epipole :74-128): n_key
    (<= 7, the reference's color_set) of the m matched pairs (host keypoints, ERP pixels of an
