@@ -12,7 +12,8 @@ Host-side mirror of the reference's hot-path classes (Kitsunetic/ERP_match_eight
   i.e. what src/automatic.cpp:117-126 runs per pair, as one sequence of gfx950 kernels
   (``run`` from descriptors, ``run_images`` from the ERP images via
   ``spherical_surf.do_all_batch``, ``run_sweep`` for the drivers' rotation sweeps: one left
-  image against a right base image under a list of poses, with the surf match error).
+  image against a right base image under a list of poses, with the surf match error,
+  ``rectify_images`` on to automatic's rectified and vertical views of every pair).
 
 Every call goes through the C ABI of ``lib/liberp_match.so`` (include/erp_match.h); there is
 no CPU fallback.  Arrays are numpy (host, synchronous) or torch CUDA tensors (device,
@@ -416,6 +417,93 @@ class erp_rotation:  # noqa: N801  (reference class name)
         check(self.L.erp_vertical_rotate_dev(self.ctx.h, im.data_ptr(), W, H, out.data_ptr(),
                                              torch.cuda.current_stream().cuda_stream),
               "vertical_rotate")
+        return out
+
+    def vertical_rotate_batch(self, ims, fill: int = 0, out=None):
+        """vertical_rotate for a stack: CUDA uint8 [n, H, W, 3] -> [n, W, H, 3], byte for byte
+        what n vertical_rotate calls give (erp_vertical_rotate_batch_dev: the source index of
+        an output pixel is computed once for all n images).  ``out``: a caller's output stack;
+        fill=-1 then leaves its unwritten pixels as they are."""
+        import torch
+        ims, _ = _image_batch_dev(ims, ims)
+        self._on_device(ims)
+        n, H, W = ims.shape[:3]
+        if out is None:
+            if fill < 0:
+                raise ValueError("fill=-1 needs the caller's out")
+            out = torch.empty((n, W, H, 3), dtype=torch.uint8, device=ims.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8
+                  and out.is_contiguous() and out.shape == (n, W, H, 3)
+                  and out.device == ims.device):
+            raise ValueError("out is a contiguous CUDA uint8 tensor [n, W, H, 3] on ims' device")
+        check(self.L.erp_vertical_rotate_batch_dev(
+            self.ctx.h, ims.data_ptr() if n else None, n, W, H, int(fill),
+            out.data_ptr() if n else None, torch.cuda.current_stream(ims.device).cuda_stream),
+            "erp_vertical_rotate_batch_dev")
+        return out
+
+    def _on_device(self, t):
+        if t.device.index != self.ctx.device:
+            raise ValueError(f"images must be on the context's device cuda:{self.ctx.device}")
+
+    def rectify_batch(self, lefts, rights, rot_vecs=None, t_vecs=None, results=None,
+                      vertical: bool = True, fill: int = 0, skip=None):
+        """What src/automatic.cpp:138-160 produces, for P pairs in one call: CUDA uint8
+        [P, H, W, 3] left / right stacks -> {"left_rectified", "right_rectified" [P, H, W, 3],
+        "done" int32 [P], and with ``vertical`` "left_vertical", "right_vertical" [P, W, H, 3]}.
+        The poses are either host ``rot_vecs`` / ``t_vecs`` [P, 3] (float64, as rectify takes
+        them; ``skip`` [P]: non-zero leaves a pair out) or ``results``, the device records of
+        PairBatchRunner.run / run_images (uint8 [P, 64]; R, T widened to double, pairs whose
+        status is not ok left out -- one readback of the records).  A pair left out or with a
+        rejected pose has done = 0 and fill-valued rectified images.  Per pair the bytes are
+        rectify's and vertical_rotate's."""
+        import torch
+        lefts, rights = _image_batch_dev(lefts, rights)
+        self._on_device(lefts)
+        n, H, W = lefts.shape[:3]
+        if (results is None) == (rot_vecs is None and t_vecs is None) or \
+                (rot_vecs is None) != (t_vecs is None):
+            raise ValueError("give either rot_vecs and t_vecs or results")
+        if not 0 <= int(fill) <= 255:
+            raise ValueError("fill is a byte value")
+        dev = lefts.device
+        u8 = dict(dtype=torch.uint8, device=dev)
+        out = {"left_rectified": torch.empty((n, H, W, 3), **u8),
+               "right_rectified": torch.empty((n, H, W, 3), **u8),
+               "done": torch.zeros(n, dtype=torch.int32, device=dev)}
+        if vertical:
+            out["left_vertical"] = torch.empty((n, W, H, 3), **u8)
+            out["right_vertical"] = torch.empty((n, W, H, 3), **u8)
+        ptr = lambda t: t.data_ptr() if n else None  # noqa: E731
+        o = capi.RectifyOutputs(ptr(out["left_rectified"]), ptr(out["right_rectified"]),
+                                ptr(out["left_vertical"]) if vertical else None,
+                                ptr(out["right_vertical"]) if vertical else None, ptr(out["done"]))
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if results is not None:
+            if skip is not None:
+                raise ValueError("skip goes with host poses; records carry their status")
+            if not (isinstance(results, torch.Tensor) and results.is_cuda
+                    and results.dtype == torch.uint8 and results.is_contiguous()
+                    and results.shape == (n, RESULT_DTYPE.itemsize) and results.device == dev):
+                raise ValueError("results is a contiguous CUDA uint8 tensor [P, 64] of "
+                                 "erp_pair_result records on the images' device")
+            check(self.L.erp_rectify_results_dev(self.ctx.h, ptr(lefts), ptr(rights), n, W, H,
+                                                 ptr(results), int(fill), C.byref(o), st),
+                  "erp_rectify_results_dev")
+            return out
+        rv = np.ascontiguousarray(rot_vecs, np.float64).reshape(-1, 3)
+        tv = np.ascontiguousarray(t_vecs, np.float64).reshape(-1, 3)
+        if rv.shape[0] != n or tv.shape[0] != n:
+            raise ValueError("rot_vecs and t_vecs are [P, 3]")
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32).reshape(-1)
+            if sk.shape[0] != n:
+                raise ValueError("skip is [P]")
+        check(self.L.erp_rectify_batch_dev(self.ctx.h, ptr(lefts), ptr(rights), n, W, H,
+                                           _np_ptr(rv), _np_ptr(tv),
+                                           _np_ptr(sk) if sk is not None else None, int(fill),
+                                           C.byref(o), st), "erp_rectify_batch_dev")
         return out
 
 
@@ -834,6 +922,18 @@ class PairBatchRunner:
                                            surf_params, launch, "erp_image_pairs_run")
         self.last_info = ss.last_info
         return {"results": res[:n_pairs]}
+
+    def rectify_images(self, lefts, rights, ratio: float = 0.3, vertical: bool = True,
+                       rect_fill: int = 0, **run_images_kwargs):
+        """automatic's main (src/automatic.cpp:81-164) for a batch: run_images, then
+        erp_rotation.rectify_batch on its device records -> run_images' dict plus
+        left_rectified, right_rectified, done and (``vertical``) left_vertical, right_vertical.
+        A pair whose status is not ok has done = 0 and rect_fill-valued rectified images."""
+        outs = dict(self.run_images(lefts, rights, ratio=ratio, **run_images_kwargs))
+        outs.update(erp_rotation(ctx=self.ctx).rectify_batch(
+            lefts, rights, results=outs["results"].contiguous(), vertical=vertical,
+            fill=rect_fill))
+        return outs
 
     def run_sweep(self, left, right_base, rot_mats, ratio: float = 0.3, want=(),
                   match_error: bool = True, chunk: int = 128, max_kp: int = 16384, fill: int = 0,

@@ -101,7 +101,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_rand_stream_set", "erp_rand_stream_advance", "erp_rand_stream_process",
             "erp_ctx_set_rand_stream", "erp_ctx_get_rand_stream",
             "erp_rand_stream_shuffle_prefix", "erp_image_sweep_features_dev",
-            "erp_image_sweep_run", "erp_match_error_dev"]
+            "erp_image_sweep_run", "erp_match_error_dev", "erp_vertical_rotate_batch_dev",
+            "erp_rectify_batch_dev", "erp_rectify_results_dev", "erp_rectify_matrices_results"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -110,7 +111,7 @@ STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eige
 OPTIONS = {"small_batch": 0, "sampler_lat": 1, "sampler_split": 2, "gram_tiles": 3,
            "zoom_levels": 4, "small_zoom": 5, "lip2": 6, "lipg": 7, "refine_hint": 8,
            "flat_refs": 9, "bound_ratio": 10, "debug_stages": 11, "debug_snap": 12,
-           "sampler_tiers": 13}
+           "sampler_tiers": 13, "vertical_shared": 14}
 MATCHER_MFMA_FILTER = 0  # erp_matcher_method
 MATCHER_VALU_EXACT = 1
 
@@ -133,6 +134,12 @@ class ImageBatchInfo(C.Structure):
 
 
 assert C.sizeof(PackedPairs) == 88 and C.sizeof(ImageBatchInfo) == 40
+
+
+class RectifyOutputs(C.Structure):
+    _fields_ = [("left_rect", P), ("right_rect", P), ("left_vertical", P), ("right_vertical", P),
+                ("done", P)]
+
 
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
@@ -216,6 +223,13 @@ def load(build_if_missing: bool = False):
     L.erp_inv3.argtypes = [P, P]
     L.erp_inv3.restype = C.c_int32
     L.erp_rectify_matrices.argtypes = [P, P, P, P]
+    L.erp_vertical_rotate_batch_dev.argtypes = [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                P, P]
+    L.erp_rectify_batch_dev.argtypes = [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, P, P,
+                                        C.c_int32, C.POINTER(RectifyOutputs), P]
+    L.erp_rectify_results_dev.argtypes = [P, P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32,
+                                          C.POINTER(RectifyOutputs), P]
+    L.erp_rectify_matrices_results.argtypes = [P, C.c_int32, P, P, P]
     L.erp_consensus_hyps_shard_dev.argtypes = [P, C.c_int32, P, C.c_int32, C.POINTER(RansacCfg),
                                                C.c_int32, C.c_int32, P, P, P, P]
     L.erp_consensus_hyps_finish_dev.argtypes = [P, C.c_int32, P, C.c_int32, C.POINTER(RansacCfg),

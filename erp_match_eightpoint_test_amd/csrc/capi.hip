@@ -155,7 +155,8 @@ struct erp_ctx {
         1,   // BOUND_RATIO: the matcher's ratio test from the bf16 bounds where they suffice
         -1,  // DEBUG_STAGES: every stage group
         0,   // DEBUG_SNAP
-        -1}; // SAMPLER_TIERS: auto
+        -1,  // SAMPLER_TIERS: auto
+        1};  // VERTICAL_SHARED: the batched vertical stage's shared-map kernel
     // debug (ERP_OPT_DEBUG_SNAP): lb, ub and the first-stage list counts right after the bounds
     // pass, fetched with erp_debug_snapshot
     DevBuf snap;

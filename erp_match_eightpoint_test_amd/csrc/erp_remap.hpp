@@ -47,6 +47,45 @@ struct RemapScratch {
 hipError_t launch_remap(const RemapJobs& jobs, int n_jobs, int max_out_rows, int max_out_cols,
                         int W, int H, const RemapScratch& scr, hipStream_t st);
 
+// ONE remap geometry applied to many images (the vertical view's fixed matrix over a batch):
+// the source index of an output pixel is the same for every image, so a thread computes it once
+// and copies the pixel for every image (remap_shared_kernel).  job gives the geometry -- mode
+// (CROP, FULL or ROT90; not COPY), m, row0, rows -- and the first image: image i of the stack is
+// job.src + i * src_stride -> job.dst + i * dst_stride (bytes), i < n.  src2 / dst2: an optional
+// second stack of n images with the same strides (the right images of a pair batch; NULL = none).
+// Sources and destinations must not overlap.
+struct RemapSharedArgs {
+    RemapJob job;
+    const uint8_t* src2;
+    uint8_t* dst2;
+    int64_t src_stride, dst_stride;
+    int32_t n;       // images per stack
+    int32_t chunks;  // set by launch_remap_shared: ceil(n / kRemapSharedChunk)
+};
+
+// Images per block of the shared-map kernel.  A launch has one grid z-slice per stack and chunk
+// of kRemapSharedChunk images, and every slice computes the index again: 16 bounds that
+// recomputation at 1/16 of the per-image kernel's arithmetic per image, while batches beyond
+// 16 images still spread over more slices (an image size with few blocks needs them to fill
+// the device).
+constexpr int kRemapSharedChunk = 16;
+
+// the boundary list of a shared-map launch: output pixel indices, one entry per output pixel
+// at most (only the first slice appends; the fix-up copies the pixel for every image)
+struct RemapSharedScratch {
+    uint32_t* count;        // device counter (zeroed by launch_remap_shared)
+    uint32_t* list;         // [out_rows * out_cols]
+};
+
+// the shared-map launch + its boundary fix-up launch; hipErrorInvalidValue for mode COPY or a
+// negative n, nothing to do for n == 0.  a.chunks is ignored on input.
+hipError_t launch_remap_shared(const RemapSharedArgs& a, int W, int H,
+                               const RemapSharedScratch& scr, hipStream_t st);
+
+// d_out[i] = h_flags[i] != 0 for i < n (int32), from host flags passed as kernel arguments: no
+// host memory is read after the call returns
+hipError_t launch_set_flags(int32_t* d_out, const int32_t* h_flags, int n, hipStream_t st);
+
 struct BandKeypointArgs {
     double m[4][9];     // per band: rotate_keypoint's matrix (unused for shift_band)
     int32_t end[4];     // exclusive end index of each band's segment in the concatenated list

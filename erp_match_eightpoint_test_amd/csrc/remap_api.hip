@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "../../include/erp_match.h"
 #include "erp_device.hpp"
@@ -59,6 +60,112 @@ bool scratch(erp_ctx* ctx, size_t pixels, erp::RemapScratch* scr) {
 
 bool dims_ok(int32_t W, int32_t H) {
     return W > 0 && H > 0 && (int64_t)W * H <= ((int64_t)1 << 31) / 3;
+}
+
+// the matrix rotate_pixel applies in the vertical view (src/automatic.cpp:146-151):
+// rot_mat_90deg = eular2rot(Vec3d(RAD(89.999), 0, 0)).inv(); rotate_image inverts it again
+bool vertical_matrix(double m[9]) {
+    const double th[3] = {erp::kPi * (89.999) / 180.0, 0, 0};
+    double R[9], Ri[9];
+    erp_eular2rot(th, R);
+    return erp_inv3(R, Ri) && erp_inv3(Ri, m);
+}
+
+bool fill_ok(int32_t fill) { return fill >= -1 && fill <= 255; }
+
+// The vertical views of one or two stacks of n images each (src2 / dst2 may be NULL), H x W x 3
+// -> W x H x 3, images and views contiguous in their stacks.  Route ERP_OPT_VERTICAL_SHARED: one
+// shared-map launch over every image (the matrix is the same for all of them), or ROT90 jobs of
+// launch_remap, kMaxRemapJobs per launch; the bytes are the same.  The boundary list of either
+// route lives in scratch slot 0 (the shared map's needs 4 bytes per pixel of the slot's 64).
+erp_status vertical_enqueue(erp_ctx* ctx, const uint8_t* src, uint8_t* dst, const uint8_t* src2,
+                            uint8_t* dst2, int32_t n, int32_t W, int32_t H, hipStream_t st) {
+    if (n <= 0) return ERP_OK;
+    erp::RemapScratch scr;
+    if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
+    const int64_t img = (int64_t)W * H * 3;
+    erp::RemapJob g{};
+    if (!vertical_matrix(g.m)) return ERP_INTERNAL;
+    g.row0 = 0;
+    g.rows = H;
+    g.mode = erp::kRemapRot90;
+    int32_t shared = 1;
+    if (erp_ctx_get_option(ctx, ERP_OPT_VERTICAL_SHARED, &shared) != ERP_OK) return ERP_INTERNAL;
+    if (shared) {
+        erp::RemapSharedArgs a{};
+        a.job = g;
+        a.job.src = src;
+        a.job.dst = dst;
+        a.src2 = src2;
+        a.dst2 = dst2;
+        a.src_stride = a.dst_stride = img;
+        a.n = n;
+        const erp::RemapSharedScratch sscr{scr.count, (uint32_t*)scr.list};
+        return erp::launch_remap_shared(a, W, H, sscr, st) == hipSuccess ? ERP_OK : ERP_HIP_ERROR;
+    }
+    const int64_t total = (int64_t)n * (src2 ? 2 : 1);
+    for (int64_t i0 = 0; i0 < total; i0 += erp::kMaxRemapJobs) {
+        erp::RemapJobs jobs{};
+        const int nj = (int)std::min<int64_t>(total - i0, erp::kMaxRemapJobs);
+        for (int k = 0; k < nj; k++) {
+            const int64_t i = i0 + k;
+            jobs.j[k] = g;
+            jobs.j[k].src = (i < n ? src : src2) + (i % n) * img;
+            jobs.j[k].dst = (i < n ? dst : dst2) + (i % n) * img;
+        }
+        if (erp::launch_remap(jobs, nj, W, H, W, H, scr, st) != hipSuccess) return ERP_HIP_ERROR;
+    }
+    return ERP_OK;
+}
+
+// fill in 0..255: the byte every output starts from; -1: as the caller left it
+bool prefill(uint8_t* d, int32_t fill, size_t bytes, hipStream_t st) {
+    return fill < 0 || !d || bytes == 0 || hipMemsetAsync(d, fill, bytes, st) == hipSuccess;
+}
+
+// erp_rectify_batch_dev / erp_rectify_results_dev after their argument checks, inside the call
+// section: pair p is remapped by m_left / m_right [n_pairs][9] where ok[p], FULL jobs through
+// launch_remap kMaxRemapJobs per launch, then the vertical stage over all 2 n_pairs rectified
+// images (a pair not remapped contributes its fill-valued images)
+erp_status rectify_batch_enqueue(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                                 int32_t n_pairs, int32_t W, int32_t H, const double* m_left,
+                                 const double* m_right, const int32_t* ok, int32_t fill,
+                                 const erp_rectify_outputs& o, hipStream_t st) {
+    erp::RemapScratch scr;
+    if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
+    const size_t img = (size_t)W * H * 3, all = img * n_pairs;
+    if (!prefill(o.left_rect, fill, all, st) || !prefill(o.right_rect, fill, all, st) ||
+        !prefill(o.left_vertical, fill, all, st) || !prefill(o.right_vertical, fill, all, st))
+        return ERP_HIP_ERROR;
+    erp::RemapJobs jobs{};
+    int nj = 0;
+    for (int32_t p = 0; p <= n_pairs; p++) {
+        if (p < n_pairs && ok[p])
+            for (int k = 0; k < 2; k++) {
+                erp::RemapJob& j = jobs.j[nj++];
+                j.src = (k ? d_right : d_left) + (size_t)p * img;
+                j.dst = (k ? o.right_rect : o.left_rect) + (size_t)p * img;
+                memcpy(j.m, (k ? m_right : m_left) + (size_t)p * 9, sizeof(j.m));
+                j.row0 = 0;
+                j.rows = H;
+                j.mode = erp::kRemapFull;
+            }
+        if (nj == erp::kMaxRemapJobs || (p == n_pairs && nj > 0)) {
+            if (erp::launch_remap(jobs, nj, H, W, W, H, scr, st) != hipSuccess)
+                return ERP_HIP_ERROR;
+            nj = 0;
+        }
+    }
+    if (o.done && erp::launch_set_flags(o.done, ok, n_pairs, st) != hipSuccess)
+        return ERP_HIP_ERROR;
+    if (!o.left_vertical) return ERP_OK;
+    return vertical_enqueue(ctx, o.left_rect, o.left_vertical, o.right_rect, o.right_vertical,
+                            n_pairs, W, H, st);
+}
+
+// the argument checks the two batched rectify entries share (n_pairs > 0)
+bool rectify_outputs_ok(const erp_rectify_outputs* o) {
+    return o && o->left_rect && o->right_rect && !o->left_vertical == !o->right_vertical;
 }
 
 }  // namespace
@@ -331,13 +438,9 @@ erp_status erp_vertical_rotate_dev(erp_ctx* ctx, const uint8_t* d_im, int32_t W,
     CtxCallGuard call(ctx, (hipStream_t)stream);
     erp::RemapScratch scr;
     if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
-    // rot_mat_90deg = eular2rot(Vec3d(RAD(89.999), 0, 0)).inv(); rotate_image inverts it again
-    const double th[3] = {erp::kPi * (89.999) / 180.0, 0, 0};
-    double R[9], Ri[9];
-    erp_eular2rot(th, R);
     erp::RemapJobs jobs{};
     erp::RemapJob& j = jobs.j[0];
-    if (!erp_inv3(R, Ri) || !erp_inv3(Ri, j.m)) return ERP_INVALID_ARG;
+    if (!vertical_matrix(j.m)) return ERP_INVALID_ARG;
     j.src = d_im;
     j.dst = d_out;
     j.row0 = 0;
@@ -345,6 +448,81 @@ erp_status erp_vertical_rotate_dev(erp_ctx* ctx, const uint8_t* d_im, int32_t W,
     j.mode = erp::kRemapRot90;
     return erp::launch_remap(jobs, 1, W, H, W, H, scr, (hipStream_t)stream) == hipSuccess
                ? ERP_OK : ERP_HIP_ERROR;
+}
+
+erp_status erp_vertical_rotate_batch_dev(erp_ctx* ctx, const uint8_t* d_ims, int32_t n, int32_t W,
+                                         int32_t H, int32_t fill, uint8_t* d_out, void* stream) {
+    if (!ctx || n < 0 || (n > 0 && (!d_ims || !d_out)) || !dims_ok(W, H) || !fill_ok(fill))
+        return ERP_INVALID_ARG;
+    if (n == 0) return ERP_OK;
+    erp_status s = set_dev(ctx);
+    if (s != ERP_OK) return s;
+    hipStream_t st = (hipStream_t)stream;
+    CtxCallGuard call(ctx, st);
+    if (!prefill(d_out, fill, (size_t)n * W * H * 3, st)) return ERP_HIP_ERROR;
+    return vertical_enqueue(ctx, d_ims, d_out, nullptr, nullptr, n, W, H, st);
+}
+
+erp_status erp_rectify_batch_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                                 int32_t n_pairs, int32_t W, int32_t H, const double* h_rot_vec,
+                                 const double* h_t_vec, const int32_t* h_skip, int32_t fill,
+                                 const erp_rectify_outputs* outputs, void* stream) {
+    if (!ctx || n_pairs < 0 || !dims_ok(W, H) || !fill_ok(fill)) return ERP_INVALID_ARG;
+    if (n_pairs == 0) return ERP_OK;
+    if (!d_left || !d_right || !h_rot_vec || !h_t_vec || !rectify_outputs_ok(outputs))
+        return ERP_INVALID_ARG;
+    std::vector<double> m((size_t)n_pairs * 18);
+    std::vector<int32_t> ok(n_pairs);
+    for (int32_t p = 0; p < n_pairs; p++)
+        ok[p] = !(h_skip && h_skip[p]) &&
+                erp_rectify_matrices(h_rot_vec + (size_t)p * 3, h_t_vec + (size_t)p * 3,
+                                     &m[(size_t)p * 9], &m[(size_t)(n_pairs + p) * 9]) == ERP_OK;
+    erp_status s = set_dev(ctx);
+    if (s != ERP_OK) return s;
+    CtxCallGuard call(ctx, (hipStream_t)stream);
+    return rectify_batch_enqueue(ctx, d_left, d_right, n_pairs, W, H, m.data(),
+                                 m.data() + (size_t)n_pairs * 9, ok.data(), fill, *outputs,
+                                 (hipStream_t)stream);
+}
+
+erp_status erp_rectify_matrices_results(const erp_pair_result* h_results, int32_t n,
+                                        double* m_left, double* m_right, int32_t* ok) {
+    if (n < 0 || (n > 0 && (!h_results || !m_left || !m_right || !ok))) return ERP_INVALID_ARG;
+    for (int32_t p = 0; p < n; p++) {
+        const erp_pair_result& r = h_results[p];
+        // Vec3d(R_vec_out), Vec3d(T_vec_out): src/automatic.cpp:128-129
+        const double rv[3] = {(double)r.R[0], (double)r.R[1], (double)r.R[2]};
+        const double tv[3] = {(double)r.T[0], (double)r.T[1], (double)r.T[2]};
+        ok[p] = r.status == ERP_OK &&
+                erp_rectify_matrices(rv, tv, m_left + (size_t)p * 9, m_right + (size_t)p * 9) ==
+                    ERP_OK;
+    }
+    return ERP_OK;
+}
+
+erp_status erp_rectify_results_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                                   int32_t n_pairs, int32_t W, int32_t H,
+                                   const erp_pair_result* d_results, int32_t fill,
+                                   const erp_rectify_outputs* outputs, void* stream) {
+    if (!ctx || n_pairs < 0 || !dims_ok(W, H) || !fill_ok(fill)) return ERP_INVALID_ARG;
+    if (n_pairs == 0) return ERP_OK;
+    if (!d_left || !d_right || !d_results || !rectify_outputs_ok(outputs)) return ERP_INVALID_ARG;
+    erp_status s = set_dev(ctx);
+    if (s != ERP_OK) return s;
+    hipStream_t st = (hipStream_t)stream;
+    CtxCallGuard call(ctx, st);
+    std::vector<erp_pair_result> rec(n_pairs);
+    if (hipMemcpyAsync(rec.data(), d_results, rec.size() * sizeof(erp_pair_result),
+                       hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return ERP_HIP_ERROR;
+    std::vector<double> m((size_t)n_pairs * 18);
+    std::vector<int32_t> ok(n_pairs);
+    double* m_right = m.data() + (size_t)n_pairs * 9;
+    s = erp_rectify_matrices_results(rec.data(), n_pairs, m.data(), m_right, ok.data());
+    if (s != ERP_OK) return s;
+    return rectify_batch_enqueue(ctx, d_left, d_right, n_pairs, W, H, m.data(), m_right, ok.data(),
+                                 fill, *outputs, st);
 }
 
 }  // extern "C"

@@ -311,6 +311,10 @@ erp_status erp_ctx_set_graphs(erp_ctx* ctx, int32_t enable);
                           configs[4]'s one 100k-iteration find, run faster without them)
    ERP_OPT_BOUND_RATIO    the matcher's ratio test decided from the bf16 bounds where they
                           suffice 1 (default) / 0
+   ERP_OPT_VERTICAL_SHARED  the vertical stage of the batched rectification
+                          (erp_vertical_rotate_batch_dev, erp_rectify_batch_dev): 1 (default)
+                          one shared-map launch over every image, 0 ROT90 jobs of the per-image
+                          remap kernel, 8 per launch
    ERP_OPT_DEBUG_STAGES   debug: bit mask of the stage groups erp_pair_batch_run enqueues (1
                           matcher + gather, 2 jump polynomials + windows, 4 sampler, 8 Gram, 32
                           eigen + estimate, 16 consensus); -1 (default) all.  A skipped group
@@ -333,7 +337,8 @@ typedef enum erp_ctx_option {
     ERP_OPT_DEBUG_STAGES = 11,
     ERP_OPT_DEBUG_SNAP = 12,
     ERP_OPT_SAMPLER_TIERS = 13,
-    ERP_OPT_COUNT = 14
+    ERP_OPT_VERTICAL_SHARED = 14,
+    ERP_OPT_COUNT = 15
 } erp_ctx_option;
 /* ERP_INVALID_ARG for an unknown option or a value outside its range */
 erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value);
@@ -454,6 +459,47 @@ erp_status erp_rectify_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d
    .inv(), then cv::rotate(ROTATE_90_CLOCKWISE), fused -> d_out W x H x 3 (W rows). */
 erp_status erp_vertical_rotate_dev(erp_ctx* ctx, const uint8_t* d_im, int32_t W, int32_t H,
                                    uint8_t* d_out, void* stream);
+/* ---- batched rectification: what src/automatic.cpp:138-160 produces, for many pairs ----
+   Images lie one after the other in their stacks ([n][H][W][3] in, [n][W][H][3] vertical views).
+   `fill` in 0..255 pre-fills every output with that byte; -1 leaves the outputs as the caller
+   set them (pixels without a source stay unwritten, as above).  Outputs must not overlap the
+   inputs or each other.  n == 0 / n_pairs == 0: ERP_OK, nothing is done. */
+/* erp_vertical_rotate_dev for n images: d_ims [n][H][W][3] -> d_out [n][W][H][3], byte for
+   byte what n calls give.  The vertical view applies one fixed matrix, so the source pixel of
+   an output pixel is computed once and copied for all n images (ERP_OPT_VERTICAL_SHARED).
+   Asynchronous on `stream`. */
+erp_status erp_vertical_rotate_batch_dev(erp_ctx* ctx, const uint8_t* d_ims, int32_t n, int32_t W,
+                                         int32_t H, int32_t fill, uint8_t* d_out, void* stream);
+/* caller-owned device outputs of the batched rectification */
+typedef struct erp_rectify_outputs {
+    uint8_t* left_rect;         /* [n_pairs][H][W][3] (required) */
+    uint8_t* right_rect;        /* [n_pairs][H][W][3] (required) */
+    uint8_t* left_vertical;     /* [n_pairs][W][H][3]; both NULL = no vertical stage */
+    uint8_t* right_vertical;    /* [n_pairs][W][H][3] */
+    int32_t* done;              /* [n_pairs] 1 = the pair's images were written, 0 = not; may be
+                                   NULL */
+} erp_rectify_outputs;
+/* rectify (src/automatic.cpp:66-79) of n_pairs pairs d_left / d_right [n_pairs][H][W][3], then
+   the two vertical views of every pair (:146-153).  h_rot_vec / h_t_vec [n_pairs][3] doubles on
+   the HOST (read before the call returns) go through erp_rectify_matrices per pair; a pair it
+   rejects, or whose h_skip entry ([n_pairs] int32 on the host, may be NULL) is non-zero, is not
+   remapped: done = 0 and its rectified images stay at `fill` -- not an error of the call.  The
+   vertical stage runs over all 2 n_pairs rectified images, so such a pair's vertical views are
+   those of its fill-valued (or, with fill = -1, caller-set) rectified images.  Per pair the
+   bytes are erp_rectify_dev's and erp_vertical_rotate_dev's.  Asynchronous on `stream`. */
+erp_status erp_rectify_batch_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                                 int32_t n_pairs, int32_t W, int32_t H, const double* h_rot_vec,
+                                 const double* h_t_vec, const int32_t* h_skip, int32_t fill,
+                                 const erp_rectify_outputs* outputs, void* stream);
+/* erp_rectify_batch_dev with the poses of device records d_results [n_pairs] (what
+   erp_pair_batch_run / erp_image_pairs_run write): R and T widened float -> double as
+   src/automatic.cpp:128-129 does (erp_rectify_matrices_results); a pair whose status is not
+   ERP_OK is skipped.  NOT graph-capturable and not asynchronous: one device-to-host copy of the
+   records and one synchronisation of `stream` precede the launches. */
+erp_status erp_rectify_results_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                                   int32_t n_pairs, int32_t W, int32_t H,
+                                   const erp_pair_result* d_results, int32_t fill,
+                                   const erp_rectify_outputs* outputs, void* stream);
 /* ---- SURF: feature_matcher::detect_key_point + comput_descriptor
    (src/feature_matcher.cpp:26-40) with xfeatures2d::SURF::create() defaults ---- */
 typedef struct erp_keypoint {   /* cv::KeyPoint layout */
@@ -664,6 +710,11 @@ int32_t erp_inv3(const double m[9], double out[9]);            /* cv::Mat::inv()
 /* the two matrices rotate_pixel applies in rectify's rotate_image calls */
 erp_status erp_rectify_matrices(const double rot_vec[3], const double t_vec[3], double m_left[9],
                                 double m_right[9]);
+/* host records -> the matrices of erp_rectify_results_dev (which goes through this): per record
+   R, T widened to double, then erp_rectify_matrices into m_left / m_right [n][9]; ok[p] = 0
+   (matrices unspecified) where status != ERP_OK or the pose is rejected, else 1 */
+erp_status erp_rectify_matrices_results(const erp_pair_result* h_results, int32_t n,
+                                        double* m_left, double* m_right, int32_t* ok);
 
 #ifdef __cplusplus
 }
