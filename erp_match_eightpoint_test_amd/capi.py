@@ -111,7 +111,7 @@ STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eige
 OPTIONS = {"small_batch": 0, "sampler_lat": 1, "sampler_split": 2, "gram_tiles": 3,
            "zoom_levels": 4, "small_zoom": 5, "lip2": 6, "lipg": 7, "refine_hint": 8,
            "flat_refs": 9, "bound_ratio": 10, "debug_stages": 11, "debug_snap": 12,
-           "sampler_tiers": 13, "vertical_shared": 14}
+           "sampler_tiers": 13, "vertical_shared": 14, "sampler_share": 15}
 MATCHER_MFMA_FILTER = 0  # erp_matcher_method
 MATCHER_VALU_EXACT = 1
 

@@ -126,7 +126,8 @@ struct erp_ctx {
     DevBuf part, part1, pu, ccount, cand, bsel, edges, gfin, matches, counts, flags, pts, polyR, polyQ, idx, gram, hyps, rv, tv, kcount, tmean,
         sortbuf, w0, off, wh, results, in_a, in_b, in_c, in_d, dscale, lb, ub, surv, nsurv, wins,
         rtab, limbs, tsplit, ovf, remap_scr, vchunk, lipref, inl, hlite,
-        w0s;                  // per-pair start windows [P][31] of a call on a rand stream
+        w0s,                  // per-pair start windows [P][31] of a call on a rand stream
+        rep;                  // the launch's alias table [P] (run_hypotheses, shared replays)
     // the attached rand stream (erp_ctx_set_rand_stream; not owned) and whether the current
     // enqueue is being captured into a graph (the stream's event is then handled around the
     // graph launch: an event inside a captured region orders nothing outside it)
@@ -156,7 +157,8 @@ struct erp_ctx {
         -1,  // DEBUG_STAGES: every stage group
         0,   // DEBUG_SNAP
         -1,  // SAMPLER_TIERS: auto
-        1};  // VERTICAL_SHARED: the batched vertical stage's shared-map kernel
+        1,   // VERTICAL_SHARED: the batched vertical stage's shared-map kernel
+        -1};  // SAMPLER_SHARE: pairs of a launch with equal match counts share one replay
     // debug (ERP_OPT_DEBUG_SNAP): lb, ub and the first-stage list counts right after the bounds
     // pass, fetched with erp_debug_snapshot
     DevBuf snap;
@@ -196,7 +198,7 @@ const CtxBuf kCtxBufs[] = {
     ERP_B(in_d, 0), ERP_B(dscale, 1), ERP_B(lb, 1), ERP_B(ub, 1), ERP_B(surv, 1),
     ERP_B(nsurv, 1), ERP_B(wins, 1), ERP_B(rtab, 1), ERP_B(limbs, 1), ERP_B(tsplit, 1),
     ERP_B(ovf, 1), ERP_B(remap_scr, 0), ERP_B(vchunk, 1), ERP_B(lipref, 1), ERP_B(inl, 1),
-    ERP_B(hlite, 1), ERP_B(w0s, 1)};
+    ERP_B(hlite, 1), ERP_B(w0s, 1), ERP_B(rep, 1)};
 #undef ERP_B
 
 #define ERP_CK(x)                                         \
@@ -463,7 +465,7 @@ erp_status ensure_estimator(erp_ctx* c, const erp::BatchShape& sh, const erp_bat
     const size_t P = (size_t)sh.n_pairs;
     const size_t nwaves = (size_t)(sh.iters + 63) / 64;
     const erp::ConsensusLayout L = erp::consensus_layout(sh.n_pairs, sh.iters);
-    bool ok = ensure(c->counts, P * 4) && ensure(c->flags, P * 4) &&
+    bool ok = ensure(c->counts, P * 4) && ensure(c->flags, P * 4) && ensure(c->rep, P * 4) &&
               ensure(c->pts, P * (sh.max_nq + 1) * 48) &&
               ensure(c->wins, P * nwaves * 31 * 64 * 4) && ensure(c->polyR, P * 65 * 31 * 4) &&
               ensure(c->polyQ, P * erp::kMaxQ * 31 * 4) &&
@@ -643,6 +645,18 @@ erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ra
     sh.sampler_tiers = c->opt[ERP_OPT_SAMPLER_TIERS];
     auto* counts = (int32_t*)c->counts.p;
     auto* flags = (int32_t*)c->flags.p;
+    // Shared replays (ERP_OPT_SAMPLER_SHARE, kernels.hip sampler_alias_kernel): with one start
+    // window for every pair, and with Philox, a pair's selection words depend on its match count
+    // alone, so pairs of this launch with equal counts share the first one's.  Not on a rand
+    // stream (every pair has its own window), not for one pair, not above the table's pair
+    // limit.  Built on the stream from the device's counts (no sync), whatever stage groups the
+    // debug mask leaves on: the table is as cheap as deciding who needs it.
+    if (c->opt[ERP_OPT_SAMPLER_SHARE] != 0 && !on_stream && sh.n_pairs >= 2 &&
+        sh.n_pairs <= erp::kAliasMaxPairs) {
+        StageTimer _t(ctx, ERP_STAGE_JUMP_PREP, st);
+        ERP_CK(erp::launch_sampler_alias(counts, sh, cfg->sample_frac, (int32_t*)c->rep.p, st));
+        sh.rep = (const int32_t*)c->rep.p;
+    }
     auto* hyps = (out && out->hyps) ? out->hyps : (erp_hypothesis*)c->hyps.p;
     const erp::ConsensusLayout L = erp::consensus_layout(sh.n_pairs, sh.iters);
     if (cfg->sampler == ERP_SAMPLER_PHILOX) {  // counter-based: no jump polynomials / windows
@@ -677,7 +691,8 @@ erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ra
                                      cfg->sample_frac, (int8_t*)c->limbs.p, (double*)c->gram.p,
                                      out ? out->samples : nullptr,
                                      ERP_FUSE_EIGEN ? (double*)c->gfin.p : nullptr,
-                                     ERP_FUSE_EIGEN == 2 ? hyps : nullptr, cfg->valid_abs, st));
+                                     ERP_FUSE_EIGEN == 2 ? hyps : nullptr, cfg->valid_abs, st,
+                                     flags));
     }
     if (c->opt[ERP_OPT_DEBUG_STAGES] & 32) {
         StageTimer _t(ctx, ERP_STAGE_EIGEN, st);
@@ -989,6 +1004,7 @@ erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value) {
         case ERP_OPT_REFINE_HINT: lo = -1; hi = 1; break;
         case ERP_OPT_DEBUG_STAGES: lo = -1; hi = 63; break;
         case ERP_OPT_SAMPLER_TIERS: lo = -1; hi = 4; break;
+        case ERP_OPT_SAMPLER_SHARE: lo = -1; hi = 1; break;
         default: break;
     }
     if (value < lo || value > hi) return ERP_INVALID_ARG;

@@ -53,6 +53,9 @@ struct BatchShape {
     // words between the pairs' glibc start windows (launch_sampler's w0): 0 = one window shared
     // by every pair (cfg's seed / offset), 31 = one per pair (a rand stream, rand_stream.hip)
     int w0_stride = 0;
+    // the launch's alias table (launch_sampler_alias: rep[p] = the pair whose jump polynomials,
+    // windows and selection words pair p uses); null = every pair produces and reads its own
+    const int32_t* rep = nullptr;
 };
 
 hipError_t launch_set_i32(int32_t* p, int32_t v, hipStream_t st);  // (values via kernel args:
@@ -100,6 +103,17 @@ hipError_t launch_bearings_direct(const erp_point2f* kl, const erp_point2f* kr, 
                                   int32_t W, int32_t H, double* pts, hipStream_t st);
 hipError_t launch_jump_prep(const int32_t* counts, const BatchShape& sh, uint32_t* polyR,
                             uint32_t* polyQ, hipStream_t st);
+// Shared replays (ERP_OPT_SAMPLER_SHARE).  With one start window for every pair (w0_stride = 0)
+// and with the Philox sampler, a pair's selection words depend on its match count alone, so pairs
+// of one launch with equal counts share one replay: rep[p] = the smallest q <= p with
+// counts[q] == counts[p], p itself for a pair the samplers skip ((int)(M sample_frac) < 1 or
+// M < 2).  One block, no host sync; launches of at most kAliasMaxPairs pairs
+// (hipErrorInvalidValue above: the caller then leaves BatchShape::rep null).  Put the table into
+// BatchShape::rep for launch_jump_prep, launch_sampler, launch_philox_sampler and
+// launch_gram_mfma; never with per-pair start windows (w0_stride != 0).
+constexpr int kAliasMaxPairs = 1024;
+hipError_t launch_sampler_alias(const int32_t* counts, const BatchShape& sh, double sample_frac,
+                                int32_t* rep, hipStream_t st);
 // ---- rand stream (rand_stream.hip): glibc rand() state that continues from call to call ----
 // host: polynomials mod P(x) = x^31 - x^28 - 1 over Z/2^32 (31 coefficients) and windows
 void glibc_poly_pow(uint64_t e, uint32_t out[31]);                   // x^e mod P, by squaring
@@ -150,11 +164,14 @@ int debug_lip_counters(uint32_t* out64);
 // s < 9 and for the iterations whose inverse iteration did not settle (evec NaN); then call
 // launch_eigen with fused = 1.  hyps != NULL as well: the settled lanes' estimates too (fused = 2:
 // the fallback and thin eigen kernels then write their own lanes' records, no estimate_kernel)
+// sh.rep != NULL: pair p reads pair rep[p]'s selection words, and flags [n_pairs] (required
+// then) gets the representative's sampler consistency bit for each aliased pair
 size_t gram_limbs_bytes(const BatchShape& sh);
 hipError_t launch_gram_mfma(const int32_t* counts, const double* pts, const uint32_t* selw,
                             const BatchShape& sh, double sample_frac, int8_t* limbs,
                             double* gram, int32_t* samples, double* evec,
-                            erp_hypothesis* hyps, double valid_abs, hipStream_t st);
+                            erp_hypothesis* hyps, double valid_abs, hipStream_t st,
+                            int32_t* flags = nullptr);
 
 // selected singular vector per iteration from the Grams gram[p][36][iters] -> evec[p][9][iters],
 // then the estimate (rank-2 fix, decomposition, Euler angles, validity) -> hyps

@@ -98,6 +98,48 @@ __global__ void bearings_direct_kernel(const erp_point2f* __restrict__ kl,
 constexpr int kPow2 = 48;  // bits of M - 1 (< 2^16) + 6 + kMaxQ (24) fit
 __constant__ uint32_t c_pow2[kPow2][31];
 
+// ---- shared replays: the alias table of a launch ---------------------------------------------
+// Without a rand stream every pair of a launch starts from one window (w0_stride = 0), so the jump
+// polynomials, the lane end windows and the whole selection-word image sel[p][w][b][lane] are
+// functions of (M, iters, sample_frac, w0) alone, and so are the Philox sampler's words (counter
+// = (iteration, draw), key = seed): two pairs with equal M get the same words.  rep[p] = the
+// smallest q <= p with counts[q] == counts[p] (p itself for a pair the samplers skip): the
+// producers (jump_prep, windows, every sampler) leave at once for a pair with rep[p] != p, and the
+// consumers (gram_mfma_kernel, samples_kernel) read pair rep[p]'s words; everything else about the
+// pair (limb images, counts, outputs) stays its own.  The representative has the same s, so it
+// sits in the same launch tier.  One block, the counts in LDS, one thread per pair comparing its
+// count with every pair's (n^2 compares on broadcast reads, 16k at 128 pairs), for launches of
+// <= kAliasMaxPairs pairs; larger ones share nothing (rep = null: the identity).
+__global__ __launch_bounds__(kAliasMaxPairs) void sampler_alias_kernel(
+    const int32_t* __restrict__ counts, int n_pairs, double sample_frac,
+    int32_t* __restrict__ rep) {
+    __shared__ __align__(16) int32_t cm[kAliasMaxPairs];
+    const int p = threadIdx.x;  // (< blockDim.x <= kAliasMaxPairs, a multiple of 64 >= n_pairs)
+    const int M = p < n_pairs ? counts[p] : 0;
+    cm[p] = M;                  // (0 past the batch: no sampled pair has it)
+    __syncthreads();
+    if (p >= n_pairs) return;
+    // every thread reads every count, four per broadcast read and no early exit: a uniform loop
+    // whose reads pipeline (the first-match scan with a break was a chain of ~n LDS round
+    // trips, 11 us at 128 pairs); min(r, q) from r = p keeps the smallest q <= p
+    const int4* c4 = reinterpret_cast<const int4*>(cm);
+    const int n4 = (n_pairs + 3) >> 2;
+    int r = p;
+#pragma unroll 8
+    for (int k = 0; k < n4; k++) {
+        const int4 c = c4[k];
+        r = c.x == M ? min(r, 4 * k) : r;
+        r = c.y == M ? min(r, 4 * k + 1) : r;
+        r = c.z == M ? min(r, 4 * k + 2) : r;
+        r = c.w == M ? min(r, 4 * k + 3) : r;
+    }
+    rep[p] = ((int)(M * sample_frac) >= 1 && M >= 2) ? r : p;
+}
+// a pair whose words another pair of the launch produces (rep = null: none)
+__device__ __forceinline__ bool sampler_aliased(const int32_t* __restrict__ rep, int p) {
+    return rep && rep[p] != p;
+}
+
 // glibc jump-ahead polynomials of one pair (one block of 16 waves):
 //   R_l = x^(l(M-1)) mod P (l = 0..64) and Q_k = x^(64(M-1) 2^k) (k < nq_needed).
 // R_1 and every Q_k are products of table powers: x^((M-1) 2^sh) = prod over the set bits b of
@@ -108,13 +150,14 @@ __constant__ uint32_t c_pow2[kPow2][31];
 __global__ __launch_bounds__(1024) void jump_prep_kernel(const int32_t* __restrict__ counts,
                                                          double sample_frac, int nq_needed,
                                                          uint32_t* __restrict__ polyR,
-                                                         uint32_t* __restrict__ polyQ) {
+                                                         uint32_t* __restrict__ polyQ,
+                                                         const int32_t* __restrict__ rep) {
     __shared__ uint32_t Rl[65][32];
     __shared__ uint32_t tq[16][2][32];
     __shared__ uint32_t fac[16][16][32];  // each wave's table factors, staged once
     const int p = blockIdx.x, lane = wave_lane(), wid = threadIdx.x >> 6;
     const int M = counts[p];
-    if ((int)(M * sample_frac) < 1 || M < 2) return;
+    if ((int)(M * sample_frac) < 1 || M < 2 || sampler_aliased(rep, p)) return;
     uint32_t cred[30];
 #pragma unroll
     for (int d = 0; d < 30; d++) cred[d] = lane < 31 ? c_red[d][lane] : 0u;
@@ -196,11 +239,12 @@ __device__ void apply_coop(const uint32_t* __restrict__ c, uint32_t* win, uint32
 __global__ __launch_bounds__(64) void sampler_window_kernel(
     const int32_t* __restrict__ counts, const uint32_t* __restrict__ polyR,
     const uint32_t* __restrict__ polyQ, const uint32_t* __restrict__ w0, int w0_stride,
-    int nwaves, double sample_frac, uint32_t* __restrict__ wins) {
+    int nwaves, double sample_frac, uint32_t* __restrict__ wins,
+    const int32_t* __restrict__ rep) {
     __shared__ uint32_t win[32], ext[64];
     const int p = blockIdx.y, w = blockIdx.x, lane = wave_lane();
     const int M = counts[p];
-    if ((int)(M * sample_frac) < 1 || M < 2) return;
+    if ((int)(M * sample_frac) < 1 || M < 2 || sampler_aliased(rep, p)) return;
     // the pair's start window (w0_stride = 0: one window shared by every pair)
     if (lane < 31) win[lane] = w0[(size_t)p * w0_stride + lane];
     __syncthreads();
@@ -761,8 +805,10 @@ __device__ __forceinline__ uint32_t replay_block(uint32_t (&ring)[31], uint32_t*
 // sel[p][w][b][lane] bit u <-> index i = M-1-31b-u (b = 0 .. (M-1)/31), exactly s bits set.
 // MODE 0: the throughput blocks on the position-major bitmap (nalloc = position words per half,
 // the allocation 2 * nalloc words), for the pairs of this launch's tier only: s in (s_lo, s_hi],
-// s_hi + 32 <= nalloc (launch_sampler; every other workgroup leaves before it touches the LDS,
-// the mode register or memory); 2 / 3: the latency blocks, step by step / positions first,
+// s_hi + 32 <= nalloc (launch_sampler; every other workgroup, and in every mode the workgroup of
+// a pair whose words its representative produces, leaves before it touches the LDS, the mode
+// register or memory -- a failed consistency check of the representative reaches its aliases'
+// flags in gram_limbs_kernel); 2 / 3: the latency blocks, step by step / positions first,
 // on the lane-major bitmap (nalloc words per lane; constants prefetched one block ahead by vector
 // loads, two blocks per loop trip so that the two constant sets alternate without register
 // copies)
@@ -770,12 +816,13 @@ template <int MODE>
 __global__ __launch_bounds__(64) void sampler_kernel(
     const int32_t* __restrict__ counts, const uint32_t* __restrict__ wins, int nwaves, int nbw,
     double sample_frac, const double* __restrict__ rtab, uint32_t* __restrict__ selw,
-    int32_t* __restrict__ flags, int nalloc, int s_lo, int s_hi) {
+    int32_t* __restrict__ flags, int nalloc, int s_lo, int s_hi,
+    const int32_t* __restrict__ rep) {
     extern __shared__ uint32_t bm[];  // MODE 0: [2][nalloc]; else [nalloc][64]
     const int p = blockIdx.y, w = blockIdx.x, lane = wave_lane();
     const int M = counts[p];
     const int s = (int)(M * sample_frac);
-    if (s < 1 || M < 2) return;
+    if (s < 1 || M < 2 || sampler_aliased(rep, p)) return;
     if (MODE == 0 && (s <= s_lo || s > s_hi)) return;  // another tier's pair
     // fp64 round-toward-zero for the rest of the wave (mod_rup_i24's fma; mod_rup stays exact
     // under it: trunc of a one-sided product, then an exact fma residual)
@@ -916,13 +963,13 @@ __device__ __forceinline__ void lat_blocks(int M, int s, int b0, int b1,
 __global__ __launch_bounds__(64 * (kSplitG + 1)) void sampler_split_kernel(
     const int32_t* __restrict__ counts, const uint32_t* __restrict__ wins, int nwaves, int nbw,
     double sample_frac, const double* __restrict__ rtab, uint32_t* __restrict__ selw,
-    int32_t* __restrict__ flags, int nalloc) {
+    int32_t* __restrict__ flags, int nalloc, const int32_t* __restrict__ rep) {
     extern __shared__ uint32_t sm[];  // H[G][nalloc][64], then B[G + 1][nalloc][64]
     __shared__ int esum[64];
     const int p = blockIdx.y, w = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int M = counts[p];
     const int s = (int)(M * sample_frac);
-    if (s < 1 || M < 2) return;  // (uniform over the workgroup)
+    if (s < 1 || M < 2 || sampler_aliased(rep, p)) return;  // (uniform over the workgroup)
     asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 2, 2), 3\n\ts_nop 3" ::: "memory");
 #if ERP_SPLIT_STAMPS
     uint64_t ts[8];
@@ -1062,19 +1109,24 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
 __global__ __launch_bounds__(64) void philox_sampler_kernel(
     const int32_t* __restrict__ counts, int iters, int nwaves, int nbw, double sample_frac,
     uint32_t seed, uint64_t offset, int nwords, uint32_t* __restrict__ selw,
-    int32_t* __restrict__ flags) {
+    int32_t* __restrict__ flags, const int32_t* __restrict__ rep) {
     extern __shared__ uint32_t bm[];  // [nwords][64]
     const int p = blockIdx.y, w = blockIdx.x, lane = wave_lane();
     const int M = counts[p];
     const int s = (int)(M * sample_frac);
     if (s < 1 || M < 2) return;
+    const bool aliased = sampler_aliased(rep, p);
     uint32_t* out = selw + ((size_t)p * nwaves + w) * (size_t)nbw * 64 + lane;
     const int nb = (M - 1) / 31 + 1;
     if ((M + 31) / 32 > nwords) {  // M beyond the per-lane LDS bitmap (> 20 480): loud status
+        // (a function of M alone: an aliased pair sets its own bit, the empty sets are its
+        // representative's)
         if (lane == 0) atomicOr(&flags[p], 8);  // ERP_INVALID_ARG; empty sets for the Gram pass
+        if (aliased) return;
         for (int b = 0; b < nb; b++) out[(size_t)b * 64] = 0u;
         return;
     }
+    if (aliased) return;
     const int mw = (M + 31) / 32;
     for (int k = 0; k < mw; k++) bm[k * 64 + lane] = 0u;
     const uint64_t h = offset + (uint64_t)(w * 64 + lane);
@@ -1181,9 +1233,18 @@ __device__ __forceinline__ int gram_swz(int n, int u) {
 __global__ __launch_bounds__(256) void gram_limbs_kernel(const int32_t* __restrict__ counts,
                                                          const double* __restrict__ pts,
                                                          int max_nq, int nbw,
-                                                         int8_t* __restrict__ limbs) {
+                                                         int8_t* __restrict__ limbs,
+                                                         const int32_t* __restrict__ rep,
+                                                         int32_t* __restrict__ flags) {
     __shared__ __align__(16) int8_t tile[kGramN * 32];
     const int p = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
+    // an aliased pair ends with the sampler bit its own replay would have set: the
+    // representative's consistency check (bit 2, set by the samplers alone and complete before
+    // this launch) -- never that pair's other flags, which belong to its own data
+    if (rep && b == 0 && tid == 0) {
+        const int r = rep[p];
+        if (r != p && (flags[r] & 2)) atomicOr(&flags[p], 2);
+    }
     const int M = counts[p];
     if (M < 2 || b > (M - 1) / 31) return;
     for (int k = tid; k < kGramN * 32 / 16; k += 256)
@@ -1385,7 +1446,7 @@ __global__ __launch_bounds__(64 * kGramWaves, GramCfg<WT>::kMinBlocks) void gram
     const int32_t* __restrict__ counts, const int8_t* __restrict__ limbs,
     const uint32_t* __restrict__ selw, int iters, int nwaves, int nbw, double sample_frac,
     double* __restrict__ gram, int nhb, double* __restrict__ evec,
-    erp_hypothesis* __restrict__ hyps, double valid_abs) {
+    erp_hypothesis* __restrict__ hyps, double valid_abs, const int32_t* __restrict__ rep) {
     using C = GramCfg<WT>;
     __shared__ __align__(16) int8_t lds[C::kRing * C::kSlotBytes];
     // XCD-aware block order (1-D grid of nhb iteration blocks x pairs): workgroups go to the 8
@@ -1405,6 +1466,9 @@ __global__ __launch_bounds__(64 * kGramWaves, GramCfg<WT>::kMinBlocks) void gram
     if (s < 1 || M < 2) return;
     const int hb = (lbk % nhb) * C::kIters;
     if (hb >= iters) return;  // uniform over the block
+    // the pair whose selection words this one reads (its own unless the launch shares replays,
+    // sampler_alias_kernel): uniform, a scalar load into an SGPR
+    const int ps = rep ? __builtin_amdgcn_readfirstlane(rep[p]) : p;
     const int nb = (M - 1) / 31 + 1;
     const int nsteps = (nb + kGramWords - 1) / kGramWords;  // words read: <= 2 nsteps - 1 <= nb < nbw
     const int h0 = hb + wv * 32 * WT;
@@ -1429,7 +1493,7 @@ __global__ __launch_bounds__(64 * kGramWaves, GramCfg<WT>::kMinBlocks) void gram
         const int d = wv * C::kSelPW + e;
         const int chunk = min((hb >> 6) + d % C::kChunks, nwaves - 1);
         dma.srs[e] = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint32_t*>(selw + ((size_t)p * nwaves + chunk) * (size_t)nbw * 64 +
+            const_cast<uint32_t*>(selw + ((size_t)ps * nwaves + chunk) * (size_t)nbw * 64 +
                                   (size_t)(d / C::kChunks) * 64),
             0, (nbw - d / C::kChunks) * 256, kBufRsrcFlags);
     }
@@ -1551,13 +1615,15 @@ __global__ __launch_bounds__(64) void samples_kernel(const int32_t* __restrict__
                                                      const uint32_t* __restrict__ selw, int iters,
                                                      int nwaves, int nbw, int idx_stride,
                                                      double sample_frac,
-                                                     int32_t* __restrict__ samples) {
+                                                     int32_t* __restrict__ samples,
+                                                     const int32_t* __restrict__ rep) {
     const int p = blockIdx.y, lane = wave_lane();
     const int h = blockIdx.x * 64 + lane;
     const int M = counts[p];
     const int s = (int)(M * sample_frac);
     if (s < 1 || M < 2 || h >= iters) return;
-    const uint32_t* sp = selw + ((size_t)p * nwaves + blockIdx.x) * (size_t)nbw * 64 + lane;
+    const int ps = rep ? rep[p] : p;  // the words' owner (sampler_alias_kernel)
+    const uint32_t* sp = selw + ((size_t)ps * nwaves + blockIdx.x) * (size_t)nbw * 64 + lane;
     int32_t* o = samples + ((size_t)p * iters + h) * idx_stride;
     int n = 0;
     for (int b = 0; b <= (M - 1) / 31; b++) {
@@ -4766,7 +4832,15 @@ hipError_t launch_jump_prep(const int32_t* counts, const BatchShape& sh, uint32_
     // sample_frac is only used to skip pairs with sample_n < 1; pass a tiny positive value so
     // every pair with M >= 2 gets polynomials (the sampler decides on its own)
     ERP_LAUNCH(jump_prep_kernel, dim3(sh.n_pairs), dim3(1024), 0, st, counts, 1.0,
-                       q_needed(sh.iters), polyR, polyQ);
+                       q_needed(sh.iters), polyR, polyQ, sh.rep);
+    return hipGetLastError();
+}
+
+hipError_t launch_sampler_alias(const int32_t* counts, const BatchShape& sh, double sample_frac,
+                                int32_t* rep, hipStream_t st) {
+    if (sh.n_pairs < 1 || sh.n_pairs > kAliasMaxPairs) return hipErrorInvalidValue;
+    ERP_LAUNCH(sampler_alias_kernel, dim3(1), dim3((sh.n_pairs + 63) / 64 * 64), 0, st, counts,
+               sh.n_pairs, sample_frac, rep);
     return hipGetLastError();
 }
 
@@ -4816,7 +4890,7 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
     const int nwaves = (sh.iters + 63) / 64;
     if (part == 0) {
         ERP_LAUNCH(sampler_window_kernel, dim3(nwaves, sh.n_pairs), dim3(64), 0, st, counts,
-                           polyR, polyQ, w0, sh.w0_stride, nwaves, sample_frac, wins);
+                           polyR, polyQ, w0, sh.w0_stride, nwaves, sample_frac, wins, sh.rep);
     } else {
         // the lane-major bitmap (latency kernels, split replay): positions 0 .. max_s, rounded up
         // to the LDS allocation granule (1280 B = 5 words per lane on gfx950,
@@ -4842,7 +4916,7 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
                               (const void*)sampler_kernel<2>, (const void*)sampler_kernel<3>};
 #define ERP_SAMPLER_LAUNCH(M, LDS, NALLOC, S_LO, S_HI)                                         \
     ERP_LAUNCH(sampler_kernel<M>, dim3(nwaves, sh.n_pairs), dim3(64), LDS, st, counts, wins,   \
-               nwaves, sh.sel_words, sample_frac, rtab, selw, flags, NALLOC, S_LO, S_HI)
+               nwaves, sh.sel_words, sample_frac, rtab, selw, flags, NALLOC, S_LO, S_HI, sh.rep)
         // the split replay (sampler_split_kernel) where the launch has <= 256 workgroups of
         // 64 iterations (one pair at <= 16k iterations) and its 7 bitmaps fit the CU's LDS;
         // sh.sampler_split (ERP_OPT_SAMPLER_SPLIT) = 0 / 1 forces it off / on (when the LDS fits)
@@ -4854,7 +4928,7 @@ hipError_t launch_sampler(const int32_t* counts, const uint32_t* polyR, const ui
             if (se != hipSuccess) return se;
             ERP_LAUNCH(sampler_split_kernel, dim3(nwaves, sh.n_pairs), dim3(64 * (kSplitG + 1)),
                        split_lds, st, counts, wins, nwaves, sh.sel_words, sample_frac, rtab, selw,
-                       flags, nwords);
+                       flags, nwords, sh.rep);
             return hipGetLastError();
         }
         const hipError_t le = ensure_dyn_lds(fns[mode], mode == 0 ? shmem_pm : shmem);
@@ -4892,7 +4966,7 @@ hipError_t launch_philox_sampler(const int32_t* counts, const BatchShape& sh, do
     if (le != hipSuccess) return le;
     ERP_LAUNCH(philox_sampler_kernel, dim3(nwaves, sh.n_pairs), dim3(64), shmem, st, counts,
                        sh.iters, nwaves, sh.sel_words, sample_frac, seed, offset, nwords, selw,
-                       flags);
+                       flags, sh.rep);
     return hipGetLastError();
 }
 
@@ -4939,10 +5013,12 @@ size_t gram_limbs_bytes(const BatchShape& sh) {
 hipError_t launch_gram_mfma(const int32_t* counts, const double* pts, const uint32_t* selw,
                             const BatchShape& sh, double sample_frac, int8_t* limbs,
                             double* gram, int32_t* samples, double* evec,
-                            erp_hypothesis* hyps, double valid_abs, hipStream_t st) {
+                            erp_hypothesis* hyps, double valid_abs, hipStream_t st,
+                            int32_t* flags) {
     const int nwaves = (sh.iters + 63) / 64;
+    if (sh.rep && !flags) return hipErrorInvalidValue;  // (the aliases' sampler bit)
     ERP_LAUNCH(gram_limbs_kernel, dim3(sh.sel_words, sh.n_pairs), dim3(256), 0, st, counts,
-                       pts, sh.max_nq, sh.sel_words, limbs);
+                       pts, sh.max_nq, sh.sel_words, limbs, sh.rep, flags);
     // row tiles per wave: 2 once the wide blocks give every CU two of them (GramCfg);
     // sh.gram_tiles (ERP_OPT_GRAM_TILES) = 1 / 2 forces one
     const int wt_force = sh.gram_tiles;
@@ -4951,16 +5027,17 @@ hipError_t launch_gram_mfma(const int32_t* counts, const double* pts, const uint
     if (wide) {
         ERP_LAUNCH(gram_mfma_kernel<2>, dim3(nhb2 * sh.n_pairs), dim3(64 * kGramWaves), 0, st, counts,
                    limbs, selw, sh.iters, nwaves, sh.sel_words, sample_frac, gram, nhb2, evec, hyps,
-                   valid_abs);
+                   valid_abs, sh.rep);
     } else {
         const int nhb = (sh.iters + GramCfg<1>::kIters - 1) / GramCfg<1>::kIters;
         ERP_LAUNCH(gram_mfma_kernel<1>, dim3(nhb * sh.n_pairs), dim3(64 * kGramWaves), 0, st, counts,
                    limbs, selw, sh.iters, nwaves, sh.sel_words, sample_frac, gram, nhb, evec, hyps,
-                   valid_abs);
+                   valid_abs, sh.rep);
     }
     if (samples)
         ERP_LAUNCH(samples_kernel, dim3(nwaves, sh.n_pairs), dim3(64), 0, st, counts, selw,
-                           sh.iters, nwaves, sh.sel_words, sh.idx_stride, sample_frac, samples);
+                           sh.iters, nwaves, sh.sel_words, sh.idx_stride, sample_frac, samples,
+                           sh.rep);
     return hipGetLastError();
 }
 

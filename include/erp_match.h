@@ -297,6 +297,12 @@ erp_status erp_ctx_set_graphs(erp_ctx* ctx, int32_t enable);
    ERP_OPT_SAMPLER_TIERS  throughput replay launches, each sizing its LDS bitmap for the pairs
                           whose sample count falls in its range: -1 auto; 0 / 1 one launch sized
                           for the batch's bound; n = 2 .. 4 at most n launches
+   ERP_OPT_SAMPLER_SHARE  pairs of one launch with equal match counts share one replay (jump
+                          polynomials, windows, selection words; glibc without a rand stream,
+                          and Philox): -1 auto = 1 on, 0 every pair replays its own.  Never on a
+                          rand stream (each pair has its own start window), for one pair, or
+                          above 1024 pairs per launch.  The saving is the share of pairs that
+                          repeat a count within the launch; none when all counts differ
    ERP_OPT_GRAM_TILES     32-iteration row tiles per Gram MFMA wave: 0 auto (2 once the launch
                           has >= 512 wide blocks), 1, 2
    ERP_OPT_ZOOM_LEVELS    the survivors' zoom levels 0 (default) .. 2
@@ -338,7 +344,8 @@ typedef enum erp_ctx_option {
     ERP_OPT_DEBUG_SNAP = 12,
     ERP_OPT_SAMPLER_TIERS = 13,
     ERP_OPT_VERTICAL_SHARED = 14,
-    ERP_OPT_COUNT = 15
+    ERP_OPT_SAMPLER_SHARE = 15,
+    ERP_OPT_COUNT = 16
 } erp_ctx_option;
 /* ERP_INVALID_ARG for an unknown option or a value outside its range */
 erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value);
