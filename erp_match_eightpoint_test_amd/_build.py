@@ -22,7 +22,7 @@ SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip
            "image_batch.hip", "rand_stream.hip", "sweep.hip",
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
-           "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp"]
+           "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp", "erp_ctx.hpp"]
 PUBLIC_HEADERS = ["erp_match.h", os.path.join("erp", "feature_matcher.hpp"),
                   os.path.join("erp", "eight_point.hpp"), os.path.join("erp", "rand_stream.hpp")]
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/erp_match.h"
+#include "erp_ctx.hpp"
 #include "erp_kernels.hpp"
 
 // eigen stage fused into the Gram kernel (kernels.hip gram_mfma_kernel: no Gram round trip
@@ -31,11 +32,6 @@
 
 namespace {
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t n = 0;
-};
-
 // Debug: erp_debug_set_alloc_pad(N) gives every buffer allocated afterwards N canary bytes
 // (0xA5) past its end; erp_debug_check_pads() reports buffers whose canary a kernel overwrote.
 std::atomic<size_t> g_alloc_pad{0};
@@ -43,7 +39,10 @@ size_t alloc_pad() { return g_alloc_pad.load(std::memory_order_relaxed); }
 std::mutex g_pad_mu;
 std::vector<std::pair<void*, size_t>> g_padded;
 
-// frees b (and forgets its canary record)
+}  // namespace
+
+namespace erp {
+
 void free_buf(DevBuf& b) {
     if (!b.p) return;
     if (alloc_pad()) {
@@ -57,7 +56,6 @@ void free_buf(DevBuf& b) {
     b.n = 0;
 }
 
-// grow-only device buffer; returns false on allocation failure
 bool ensure(DevBuf& b, size_t bytes) {
     if (bytes == 0) bytes = 16;
     if (b.n >= bytes) return true;
@@ -75,114 +73,17 @@ bool ensure(DevBuf& b, size_t bytes) {
     return true;
 }
 
+}  // namespace erp
 
-}  // namespace
-
-// (global linkage: viz.hip shuffles on the same stream)
-// glibc rand() window before draw `offset` of a stream seeded with `seed` (host; same
-// recurrence the kernels jump along).  31 words r[n-31..n-1].  Small offsets step the
-// recurrence; above kSeqOffsets the window before draw 0 is moved on by x^offset mod P
-// (rand_stream.hip glibc_poly_pow: ~128 products of 31 x 31 words whatever the offset).
-constexpr uint64_t kSeqOffsets = 4096;
-void host_glibc_window(uint32_t seed, uint64_t offset, uint32_t out[31]) {
-    if (offset <= kSeqOffsets) return erp::glibc_window_seq(seed, offset, out);
-    erp::glibc_window_seq(seed, 0, out);
-    erp::glibc_window_jump(out, offset);
-}
-
-// A rand stream (include/erp_match.h): host state until the first GPU call that uses it, then
-// the device copy d_state (erp_kernels.hpp kStream*) is the authoritative one.
-struct erp_rand_stream {
-    std::mutex mu;            // calls take the stream in the order they lock it
-    uint32_t seed = 1;
-    uint64_t draws = 0;
-    uint32_t win[31] = {};
-    int device = -1;          // the device of d_state (a process stream: fixed from the start)
-    uint32_t* d_state = nullptr;
-    // recorded right after the last kernel that touched d_state; the next one waits for it
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    bool process_owned = false;
-};
-
-struct erp_ctx {
-    int device = 0;
-    // one lock per context; recursive so the host-pointer entry points hold it across their
-    // copies AND the device entry point they call
-    std::recursive_mutex mu;
-    // stream ordering between calls (the scratch below is shared by every call): the end of
-    // the last call's work, and the stream it was enqueued on
-    hipEvent_t done = nullptr;
-    hipStream_t last = nullptr;
-    bool pending = false;
-    // stage timing
-    bool profiling = false;
-    int32_t matcher = ERP_MATCHER_MFMA_FILTER;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    std::vector<std::pair<int, size_t>> ev_rec;  // (stage, index of start event; end = +1)
-    DevBuf mblk;              // knn2_merge's per-block survivor counts
-    DevBuf zsel;              // consensus zoom: the survivors' rank-window bins (level 1 grid)
-    DevBuf part, part1, pu, ccount, cand, bsel, edges, gfin, matches, counts, flags, pts, polyR, polyQ, idx, gram, hyps, rv, tv, kcount, tmean,
-        sortbuf, w0, off, wh, results, in_a, in_b, in_c, in_d, dscale, lb, ub, surv, nsurv, wins,
-        rtab, limbs, tsplit, ovf, remap_scr, vchunk, lipref, inl, hlite,
-        w0s,                  // per-pair start windows [P][31] of a call on a rand stream
-        rep;                  // the launch's alias table [P] (run_hypotheses, shared replays)
-    // the attached rand stream (erp_ctx_set_rand_stream; not owned) and whether the current
-    // enqueue is being captured into a graph (the stream's event is then handled around the
-    // graph launch: an event inside a captured region orders nothing outside it)
-    erp_rand_stream* rs = nullptr;
-    bool rs_capture = false;
-    DevBuf extra[24];         // erp_ctx_scratch_internal slots (1-11 SURF, 12 viz, 13-17 image
-                              // batch, 18-23 sweep: erp_image_batch.hpp)
-    // route options (erp_ctx_set_option; include/erp_match.h documents each, defaults below)
-    int32_t opt[ERP_OPT_COUNT] = {
-        -1,  // SMALL_BATCH: auto
-        -1,  // SAMPLER_LAT: auto
-        -1,  // SAMPLER_SPLIT: auto
-        0,   // GRAM_TILES: auto
-        // ZOOM_LEVELS: 0 since r05 -- with the hinted refine windows (r04) the survivors' zoom
-        // no longer pays for itself; same-box A/B per 768-pair step (profiles/r05w_ab_zoom.txt):
-        // consensus 5.81 / 5.87 -> 5.67 / 5.67 ms, worst-case batch 16.2 / 16.1k -> 16.6 /
-        // 16.5k pairs/s.  (The second pre-pruning stage's fine pass uses the zoom kernel either way.)
-        0,
-        0,   // SMALL_ZOOM: the small-batch route skips the zoom (single pair 0.487 -> 0.437 ms)
-        // LIP2 / LIPG / REFINE_HINT / FLAT_REFS: -1 = automatic (pruning_opts): on for batches of
-        // >= kFewPairs pairs, off below
-        -1,  // LIP2: the second pre-pruning stage (kernels.hip consensus_lipschitz2_kernel)
-        -1,  // LIPG: the central references' distance gradient (consensus_grad_kernel)
-        -1,  // REFINE_HINT: sub-bins on each row's Lipschitz interval (consensus_hint_kernel)
-        -1,  // FLAT_REFS: pairs whose first stage kept > 25 % of the rows take the flat route
-        1,   // BOUND_RATIO: the matcher's ratio test from the bf16 bounds where they suffice
-        -1,  // DEBUG_STAGES: every stage group
-        0,   // DEBUG_SNAP
-        -1,  // SAMPLER_TIERS: auto
-        1,   // VERTICAL_SHARED: the batched vertical stage's shared-map kernel
-        -1};  // SAMPLER_SHARE: pairs of a launch with equal match counts share one replay
-    // debug (ERP_OPT_DEBUG_SNAP): lb, ub and the first-stage list counts right after the bounds
-    // pass, fetched with erp_debug_snapshot
-    DevBuf snap;
-    size_t snap_bytes = 0;
-    uint64_t surf_key = 0;    // (W, H, params) of the SURF layer table in extra[1]
-    uint32_t viz_epoch = 0;   // stamp epoch of the draw_match line buffer (extra[12])
-    // HIP-graph replay of erp_pair_batch_run (erp_ctx_set_graphs): key bytes -> executable graph
-    bool use_graphs = false;
-    struct Graph {
-        std::vector<uint8_t> key;
-        hipGraphExec_t exec = nullptr;
-        uint64_t used = 0;
-    };
-    std::vector<Graph> graphs;
-    uint64_t graph_clock = 0;
-    bool rtab_valid = false;  // rtab[d] = 1/d rounded up (the sampler's exact modulo)
-    bool w0_valid = false;
-    uint32_t w0_seed = 0;
-    uint64_t w0_offset = 0;
-};
+using erp::CtxCall;
+using erp::DevBuf;
+using erp::HostCtxCall;
+using erp::RsTurn;
+using erp::StageTimer;
 
 // every named DevBuf of the context (extra[] and snap apart); graph = a captured
 // erp_pair_batch_run bakes its address in (graph_key).  The host-pointer entry points' staging
-// (off, wh, in_a..in_d) and remap_scr are not part of that call.
+// (off, wh, in_a..in_d) is not part of that call.
 struct CtxBuf {
     DevBuf erp_ctx::*m;
     bool graph;
@@ -197,115 +98,13 @@ const CtxBuf kCtxBufs[] = {
     ERP_B(wh, 0), ERP_B(results, 1), ERP_B(in_a, 0), ERP_B(in_b, 0), ERP_B(in_c, 0),
     ERP_B(in_d, 0), ERP_B(dscale, 1), ERP_B(lb, 1), ERP_B(ub, 1), ERP_B(surv, 1),
     ERP_B(nsurv, 1), ERP_B(wins, 1), ERP_B(rtab, 1), ERP_B(limbs, 1), ERP_B(tsplit, 1),
-    ERP_B(ovf, 1), ERP_B(remap_scr, 0), ERP_B(vchunk, 1), ERP_B(lipref, 1), ERP_B(inl, 1),
-    ERP_B(hlite, 1), ERP_B(w0s, 1), ERP_B(rep, 1)};
+    ERP_B(ovf, 1), ERP_B(vchunk, 1), ERP_B(lipref, 1), ERP_B(inl, 1), ERP_B(hlite, 1),
+    ERP_B(w0s, 1), ERP_B(rep, 1)};
 #undef ERP_B
-
-#define ERP_CK(x)                                         \
-    do {                                                  \
-        if ((x) != hipSuccess) return ERP_HIP_ERROR;      \
-    } while (0)
-
-namespace {
-
-// records an event pair around one launch when profiling is on
-struct StageTimer {
-    erp_ctx* c;
-    int stage;
-    hipStream_t st;
-    size_t idx = (size_t)-1;
-    StageTimer(erp_ctx* c_, int stage_, hipStream_t st_) : c(c_), stage(stage_), st(st_) {
-        if (!c->profiling) return;
-        while (c->ev_pool.size() < c->ev_used + 2) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return;
-            c->ev_pool.push_back(e);
-        }
-        idx = c->ev_used;
-        c->ev_used += 2;
-        (void)hipEventRecord(c->ev_pool[idx], st);
-    }
-    ~StageTimer() {
-        if (idx == (size_t)-1) return;
-        (void)hipEventRecord(c->ev_pool[idx + 1], st);
-        c->ev_rec.emplace_back(stage, idx);
-    }
-};
-
-// A call's enqueue section on a context: holds the context lock, makes this call's stream wait
-// for the previous call's work when that went to another stream (every call shares the
-// context's scratch, so two calls on different streams would otherwise race on it), and on
-// exit records the end of this call's work.  Calls on one stream stay in stream order for free.
-struct CtxCall {
-    erp_ctx* c;
-    hipStream_t st;
-    CtxCall(erp_ctx* c_, hipStream_t st_) : c(c_), st(st_) {
-        c->mu.lock();
-        if (c->pending && st != c->last) (void)hipStreamWaitEvent(st, c->done, 0);
-    }
-    ~CtxCall() {
-        if (!c->done) (void)hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
-        if (c->done && hipEventRecord(c->done, st) == hipSuccess) {
-            c->last = st;
-            c->pending = true;
-        }
-        c->mu.unlock();
-    }
-    CtxCall(const CtxCall&) = delete;
-    CtxCall& operator=(const CtxCall&) = delete;
-};
-
-// The host-pointer entry points that write the shared scratch with blocking copies (null
-// stream): join the context's call order and wait on the host for the previous call's device
-// work first -- the null stream does not synchronise with non-blocking streams, so an earlier
-// *_dev call on such a stream may still be reading the buffers about to be overwritten.
-struct HostCtxCall : CtxCall {
-    explicit HostCtxCall(erp_ctx* c_) : CtxCall(c_, nullptr) {
-        if (c->pending) (void)hipEventSynchronize(c->done);
-    }
-};
-
-}  // namespace
 
 extern "C" {
 
 int32_t erp_abi_version(void) { return ERP_MATCH_ABI_VERSION; }
-
-}  // extern "C"
-
-int32_t erp_ctx_device_internal(erp_ctx* ctx) { return ctx->device; }  // remap_api.hip
-
-// CtxCall for the entry points of remap_api.hip / surf_api.hip
-void* erp_ctx_call_begin_internal(erp_ctx* ctx, hipStream_t st) { return new CtxCall(ctx, st); }
-void erp_ctx_call_end_internal(void* call) { delete (CtxCall*)call; }
-uint64_t* erp_ctx_surf_key_internal(erp_ctx* ctx) { return &ctx->surf_key; }  // surf_api.hip
-
-// grow-only scratch slots for remap_api.hip / surf_api.hip (slot 0: remap boundary list;
-// 1..: SURF buffers)
-void* erp_ctx_scratch_internal(erp_ctx* ctx, int which, size_t bytes) {
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (which < 0 || which >= (int)(sizeof(ctx->extra) / sizeof(ctx->extra[0]))) return nullptr;
-    DevBuf& b = which == 0 ? ctx->remap_scr : ctx->extra[which];
-    return ensure(b, bytes) ? b.p : nullptr;
-}
-
-// the draw_match line buffer: grown like the other slots, with a per-call epoch for its stamps
-// (epoch << 16 | match index); *fresh = the buffer must be zeroed first (new memory, or the
-// 16-bit epoch wrapped)
-void* erp_ctx_stamp_buffer_internal(erp_ctx* ctx, size_t bytes, uint32_t* epoch, bool* fresh) {
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    DevBuf& b = ctx->extra[12];
-    // growth is detected by the size: hipMalloc may hand the freed address back for the larger
-    // block, whose tail then holds stale stamps
-    const size_t n_before = b.n;
-    if (!ensure(b, bytes)) return nullptr;
-    *fresh = b.n != n_before || ctx->viz_epoch == 0 || ctx->viz_epoch >= 0xFFFFu;
-    ctx->viz_epoch = *fresh ? 1u : ctx->viz_epoch + 1u;
-    *epoch = ctx->viz_epoch;
-    return b.p;
-}
-
-extern "C" {
 
 const char* erp_status_string(erp_status s) {
     switch (s) {
@@ -518,55 +317,13 @@ erp_status upload_w0(erp_ctx* c, const erp_ransac_cfg* cfg, hipStream_t st) {
     return ERP_OK;
 }
 
-// ---- rand stream: device side (the C entry points are at the end of this file) ----
-
-// the stream's state into device memory on `device` (once; blocking, so never inside a capture)
-erp_status rs_to_device(erp_rand_stream* s, int device) {
-    std::lock_guard<std::mutex> g(s->mu);
-    if (s->d_state) return s->device == device ? ERP_OK : ERP_INVALID_ARG;
-    if (s->device >= 0 && s->device != device) return ERP_INVALID_ARG;  // a process stream
-    uint32_t h[erp::kStreamStateWords] = {};
-    memcpy(h + erp::kStreamWin, s->win, sizeof(s->win));
-    h[erp::kStreamSeed] = s->seed;
-    memcpy(h + erp::kStreamDraws, &s->draws, 8);
-    uint32_t* d = nullptr;
-    if (hipMalloc(&d, sizeof(h)) != hipSuccess) return ERP_OUT_OF_MEMORY;
-    hipEvent_t ev = nullptr;
-    if (hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        (void)hipFree(d);
-        return ERP_HIP_ERROR;
-    }
-    s->d_state = d;
-    s->ev = ev;
-    s->device = device;
-    return ERP_OK;
-}
-
-// a stream's turn on HIP stream st: holds the stream's lock, makes st wait for the last kernel
-// that touched the state, and on exit records the end of this turn's kernels
-struct RsTurn {
-    erp_rand_stream* s;
-    hipStream_t st;
-    RsTurn(erp_rand_stream* s_, hipStream_t st_) : s(s_), st(st_) {
-        s->mu.lock();
-        if (s->pending) (void)hipStreamWaitEvent(st, s->ev, 0);
-    }
-    ~RsTurn() {
-        if (hipEventRecord(s->ev, st) == hipSuccess) s->pending = true;
-        s->mu.unlock();
-    }
-    RsTurn(const RsTurn&) = delete;
-    RsTurn& operator=(const RsTurn&) = delete;
-};
-
 // a consuming call's preparation, before anything is enqueued or captured: no Philox on a
 // stream, the per-pair windows' buffer, the state on the context's device
 erp_status stream_prepare(erp_ctx* c, const erp_ransac_cfg* cfg, size_t n_pairs) {
     if (cfg->sampler != ERP_SAMPLER_GLIBC) return ERP_INVALID_ARG;
     if (!ensure(c->w0s, n_pairs * 31 * 4) || !erp::stream_tables_ready())
         return ERP_OUT_OF_MEMORY;
-    return rs_to_device(c->rs, c->device);
+    return erp::rs_to_device(c->rs, c->device);
 }
 
 // the consuming launch (counts[P] final): every pair's start window, the state advanced.  The
@@ -725,15 +482,23 @@ PruningOpts pruning_opts(const erp_ctx* c, const erp::BatchShape& sh) {
 
 // consensus stages after the hypothesis records are in place (counts may be null when the
 // valid list is given directly: erp_consensus_dev)
-// phase: 0 = everything; 1 = compaction + bounds of rows shard / nshards only (into lb_/ub_/
-// bsel_); 2 = the rest (select onward) after a phase-1 call on this context, with the bounds
-// of every row in lb_/ub_/bsel_ (combined over the shards by the caller)
+struct ConsensusCall {
+    // 0 = everything; 1 = compaction + bounds of rows shard / nshards only (into lb / ub /
+    // bsel); 2 = the rest (select onward) after a phase-1 call on this context, with the bounds
+    // of every row in lb / ub / bsel (combined over the shards by the caller)
+    int phase = 0;
+    int shard = 0, nshards = 1;
+    double* lb = nullptr;     // the caller's bounds buffers (null: the context's)
+    double* ub = nullptr;
+    int32_t* bsel = nullptr;
+    bool lite = false;        // the estimates are in the lite layout (use_lite)
+};
 erp_status run_consensus(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_cfg* cfg,
                          const erp_batch_outputs* out, erp_pair_result* results, hipStream_t st,
-                         bool from_hyps, int phase = 0, int shard = 0, int nshards = 1,
-                         double* lb_ = nullptr, double* ub_ = nullptr, int32_t* bsel_ = nullptr,
-                         bool lite = false) {
+                         bool from_hyps, const ConsensusCall& cc = ConsensusCall()) {
     erp_ctx* ctx = c;
+    const int phase = cc.phase, shard = cc.shard, nshards = cc.nshards;
+    const bool lite = cc.lite;
     erp::ConsensusBufs cb{};
     cb.counts = from_hyps ? (int32_t*)c->counts.p : nullptr;
     cb.flags = (int32_t*)c->flags.p;  // consensus-only: set by consensus_input (non-finite)
@@ -743,9 +508,9 @@ erp_status run_consensus(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac
     cb.rv_aos = out ? out->rvec : nullptr;
     cb.dscale = (float*)c->dscale.p;
     cb.tmean = (out && out->dist) ? out->dist : (double*)c->tmean.p;
-    cb.lb = lb_ ? lb_ : (double*)c->lb.p;
-    cb.ub = ub_ ? ub_ : (double*)c->ub.p;
-    cb.bsel = bsel_ ? bsel_ : (int32_t*)c->bsel.p;
+    cb.lb = cc.lb ? cc.lb : (double*)c->lb.p;
+    cb.ub = cc.ub ? cc.ub : (double*)c->ub.p;
+    cb.bsel = cc.bsel ? cc.bsel : (int32_t*)c->bsel.p;
     cb.zsel = c->zsel.p;
     cb.surv = c->surv.p;
     cb.nsurv = c->nsurv.p;
@@ -855,8 +620,9 @@ erp_status run_estimator(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac
     es = run_hypotheses(c, sh, cfg, out, st, lite, c->rs != nullptr);
     if (es != ERP_OK) return es;
     if (!(c->opt[ERP_OPT_DEBUG_STAGES] & 16)) return ERP_OK;
-    return run_consensus(c, sh, cfg, out, results, st, true, 0, 0, 1, nullptr, nullptr, nullptr,
-                         lite);
+    ConsensusCall cc;
+    cc.lite = lite;
+    return run_consensus(c, sh, cfg, out, results, st, true, cc);
 }
 
 }  // namespace
@@ -1233,10 +999,13 @@ erp_status erp_consensus_dev(erp_ctx* ctx, const float* d_rvec, const float* d_t
     return run_consensus(ctx, sh, &cfg, nullptr, d_result, st, false);
 }
 
-erp_status erp_consensus_hyps_dev(erp_ctx* ctx, int32_t m, const erp_hypothesis* d_hyps,
-                                  int32_t n_hyps, const erp_ransac_cfg* cfg,
-                                  erp_pair_result* d_result, void* stream) {
-    if (!ctx || m < 0 || m > 65535 || n_hyps < 1 || !d_hyps || !d_result || !cfg_ok(cfg))
+// the consensus over one pair's hypothesis records (m matches, n_hyps records): the whole of
+// it, one shard's bounds or the finish, as cc says
+static erp_status consensus_hyps_call(erp_ctx* ctx, int32_t m, const erp_hypothesis* d_hyps,
+                                      int32_t n_hyps, const erp_ransac_cfg* cfg,
+                                      const ConsensusCall& cc, erp_pair_result* d_result,
+                                      void* stream) {
+    if (!ctx || m < 0 || m > 65535 || n_hyps < 1 || !d_hyps || !cfg_ok(cfg))
         return ERP_INVALID_ARG;
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
@@ -1247,54 +1016,53 @@ erp_status erp_consensus_hyps_dev(erp_ctx* ctx, int32_t m, const erp_hypothesis*
     out.hyps = const_cast<erp_hypothesis*>(d_hyps);  // read only by the consensus stages
     erp_status es = ensure_estimator(ctx, sh, &out);
     if (es != ERP_OK) return es;
-    ERP_CK(hipMemsetAsync(ctx->flags.p, 0, 4, st));
-    ERP_CK(erp::launch_set_i32((int32_t*)ctx->counts.p, m, st));
-    return run_consensus(ctx, sh, cfg, &out, d_result, st, true);
+    if (cc.phase == 1) {
+        const size_t rows = 2 * (size_t)n_hyps;
+        ERP_CK(hipMemsetAsync(cc.lb, 0, rows * 8, st));
+        ERP_CK(hipMemsetAsync(cc.ub, 0, rows * 8, st));
+        ERP_CK(hipMemsetAsync(cc.bsel, 0, rows * 8, st));
+    }
+    if (cc.phase != 2) {  // (the finish goes on from the shard calls' counts and flags)
+        ERP_CK(hipMemsetAsync(ctx->flags.p, 0, 4, st));
+        ERP_CK(erp::launch_set_i32((int32_t*)ctx->counts.p, m, st));
+    }
+    return run_consensus(ctx, sh, cfg, &out, d_result, st, true, cc);
+}
+
+erp_status erp_consensus_hyps_dev(erp_ctx* ctx, int32_t m, const erp_hypothesis* d_hyps,
+                                  int32_t n_hyps, const erp_ransac_cfg* cfg,
+                                  erp_pair_result* d_result, void* stream) {
+    if (!d_result) return ERP_INVALID_ARG;
+    return consensus_hyps_call(ctx, m, d_hyps, n_hyps, cfg, ConsensusCall(), d_result, stream);
 }
 
 erp_status erp_consensus_hyps_shard_dev(erp_ctx* ctx, int32_t m, const erp_hypothesis* d_hyps,
                                         int32_t n_hyps, const erp_ransac_cfg* cfg, int32_t shard,
                                         int32_t nshards, double* d_lb, double* d_ub,
                                         int32_t* d_bsel, void* stream) {
-    if (!ctx || m < 0 || m > 65535 || n_hyps < 1 || !d_hyps || !cfg_ok(cfg) || nshards < 1 ||
-        shard < 0 || shard >= nshards || !d_lb || !d_ub || !d_bsel)
+    if (nshards < 1 || shard < 0 || shard >= nshards || !d_lb || !d_ub || !d_bsel)
         return ERP_INVALID_ARG;
-    ERP_CK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    CtxCall call(ctx, st);
-    const erp::BatchShape sh = make_shape(1, std::max(m, 1), std::max(m, 1), n_hyps,
-                                          cfg->sample_frac);
-    erp_batch_outputs out{};
-    out.hyps = const_cast<erp_hypothesis*>(d_hyps);
-    erp_status es = ensure_estimator(ctx, sh, &out);
-    if (es != ERP_OK) return es;
-    const size_t rows = 2 * (size_t)n_hyps;
-    ERP_CK(hipMemsetAsync(d_lb, 0, rows * 8, st));
-    ERP_CK(hipMemsetAsync(d_ub, 0, rows * 8, st));
-    ERP_CK(hipMemsetAsync(d_bsel, 0, rows * 8, st));
-    ERP_CK(hipMemsetAsync(ctx->flags.p, 0, 4, st));
-    ERP_CK(erp::launch_set_i32((int32_t*)ctx->counts.p, m, st));
-    return run_consensus(ctx, sh, cfg, &out, nullptr, st, true, 1, shard, nshards, d_lb, d_ub,
-                         d_bsel);
+    ConsensusCall cc;
+    cc.phase = 1;
+    cc.shard = shard;
+    cc.nshards = nshards;
+    cc.lb = d_lb;
+    cc.ub = d_ub;
+    cc.bsel = d_bsel;
+    return consensus_hyps_call(ctx, m, d_hyps, n_hyps, cfg, cc, nullptr, stream);
 }
 
 erp_status erp_consensus_hyps_finish_dev(erp_ctx* ctx, int32_t m, const erp_hypothesis* d_hyps,
                                          int32_t n_hyps, const erp_ransac_cfg* cfg, double* d_lb,
                                          double* d_ub, int32_t* d_bsel, erp_pair_result* d_result,
                                          void* stream) {
-    if (!ctx || m < 0 || m > 65535 || n_hyps < 1 || !d_hyps || !cfg_ok(cfg) || !d_lb || !d_ub ||
-        !d_bsel || !d_result)
-        return ERP_INVALID_ARG;
-    ERP_CK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
-    CtxCall call(ctx, st);
-    const erp::BatchShape sh = make_shape(1, std::max(m, 1), std::max(m, 1), n_hyps,
-                                          cfg->sample_frac);
-    erp_batch_outputs out{};
-    out.hyps = const_cast<erp_hypothesis*>(d_hyps);
-    erp_status es = ensure_estimator(ctx, sh, &out);
-    if (es != ERP_OK) return es;
-    return run_consensus(ctx, sh, cfg, &out, d_result, st, true, 2, 0, 1, d_lb, d_ub, d_bsel);
+    if (!d_lb || !d_ub || !d_bsel || !d_result) return ERP_INVALID_ARG;
+    ConsensusCall cc;
+    cc.phase = 2;
+    cc.lb = d_lb;
+    cc.ub = d_ub;
+    cc.bsel = d_bsel;
+    return consensus_hyps_call(ctx, m, d_hyps, n_hyps, cfg, cc, d_result, stream);
 }
 
 erp_status erp_eight_point_find(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* h_kl,
@@ -1430,114 +1198,7 @@ extern "C" long long erp_debug_snapshot(erp_ctx* ctx, void* host, size_t bytes) 
     return (long long)ctx->snap_bytes;
 }
 
-// ================================================================ rand stream ==========
-erp_rand_stream* erp_ctx_rand_stream_internal(erp_ctx* ctx) { return ctx->rs; }  // viz.hip
-// viz.hip: random_shuffle(iota(m)) on the window `ring`, which ends up m - 1 draws further on
-void erp_shuffle_prefix_window(uint32_t ring[31], int32_t m, int32_t n, int32_t* h_idx);
-
-namespace {
-
-// the stream's (seed, draws, window) on the host, after its last device update; s->mu held
-erp_status rs_fetch(erp_rand_stream* s) {
-    if (!s->d_state) return ERP_OK;
-    ERP_CK(hipSetDevice(s->device));
-    if (s->pending) ERP_CK(hipEventSynchronize(s->ev));
-    uint32_t h[erp::kStreamNextWin];
-    ERP_CK(hipMemcpy(h, s->d_state, sizeof(h), hipMemcpyDeviceToHost));
-    memcpy(s->win, h + erp::kStreamWin, sizeof(s->win));
-    s->seed = h[erp::kStreamSeed];
-    memcpy(&s->draws, h + erp::kStreamDraws, 8);
-    return ERP_OK;
-}
-
-// set (seed, offset) or advance by n; s->mu held.  Host arithmetic before the first device use,
-// one wave on the device after it (ordered by the stream's event, on the null stream)
-erp_status rs_jump(erp_rand_stream* s, bool set, uint32_t seed, uint64_t n) {
-    if (set && seed == 0) seed = 1;
-    if (!s->d_state) {
-        if (set) {
-            host_glibc_window(seed, n, s->win);
-            s->seed = seed;
-            s->draws = n;
-        } else {
-            erp::glibc_window_jump(s->win, n);
-            s->draws += n;
-        }
-        return ERP_OK;
-    }
-    ERP_CK(hipSetDevice(s->device));
-    if (s->pending) ERP_CK(hipStreamWaitEvent(nullptr, s->ev, 0));
-    ERP_CK(erp::launch_stream_jump(s->d_state, set ? 1 : 0, seed, n, nullptr));
-    ERP_CK(hipEventRecord(s->ev, nullptr));
-    s->pending = true;
-    return ERP_OK;
-}
-
-std::mutex g_process_mu;
-std::vector<erp_rand_stream*> g_process_streams;  // by device, never freed
-
-}  // namespace
-
 extern "C" {
-
-erp_status erp_rand_stream_create(uint32_t seed, uint64_t offset, erp_rand_stream** out) {
-    if (!out) return ERP_INVALID_ARG;
-    erp_rand_stream* s = new (std::nothrow) erp_rand_stream();
-    if (!s) return ERP_OUT_OF_MEMORY;
-    (void)rs_jump(s, true, seed, offset);
-    *out = s;
-    return ERP_OK;
-}
-
-erp_status erp_rand_stream_destroy(erp_rand_stream* s) {
-    if (!s || s->process_owned) return ERP_INVALID_ARG;
-    if (s->d_state) {
-        (void)hipSetDevice(s->device);
-        if (s->pending) (void)hipEventSynchronize(s->ev);
-        (void)hipEventDestroy(s->ev);
-        (void)hipFree(s->d_state);
-    }
-    delete s;
-    return ERP_OK;
-}
-
-erp_status erp_rand_stream_get(erp_rand_stream* s, uint32_t* seed, uint64_t* draws) {
-    if (!s) return ERP_INVALID_ARG;
-    std::lock_guard<std::mutex> g(s->mu);
-    const erp_status es = rs_fetch(s);
-    if (es != ERP_OK) return es;
-    if (seed) *seed = s->seed;
-    if (draws) *draws = s->draws;
-    return ERP_OK;
-}
-
-erp_status erp_rand_stream_set(erp_rand_stream* s, uint32_t seed, uint64_t offset) {
-    if (!s) return ERP_INVALID_ARG;
-    std::lock_guard<std::mutex> g(s->mu);
-    return rs_jump(s, true, seed, offset);
-}
-
-erp_status erp_rand_stream_advance(erp_rand_stream* s, uint64_t n) {
-    if (!s) return ERP_INVALID_ARG;
-    std::lock_guard<std::mutex> g(s->mu);
-    return rs_jump(s, false, 0, n);
-}
-
-erp_status erp_rand_stream_process(int32_t device, erp_rand_stream** out) {
-    if (!out || device < 0 || device >= 1024) return ERP_INVALID_ARG;
-    std::lock_guard<std::mutex> g(g_process_mu);
-    if (g_process_streams.size() <= (size_t)device) g_process_streams.resize((size_t)device + 1);
-    erp_rand_stream*& s = g_process_streams[(size_t)device];
-    if (!s) {
-        s = new (std::nothrow) erp_rand_stream();
-        if (!s) return ERP_OUT_OF_MEMORY;
-        (void)rs_jump(s, true, 1, 0);
-        s->device = device;
-        s->process_owned = true;
-    }
-    *out = s;
-    return ERP_OK;
-}
 
 erp_status erp_ctx_set_rand_stream(erp_ctx* ctx, erp_rand_stream* s) {
     if (!ctx) return ERP_INVALID_ARG;
@@ -1554,25 +1215,6 @@ erp_status erp_ctx_get_rand_stream(erp_ctx* ctx, erp_rand_stream** out) {
     if (!ctx || !out) return ERP_INVALID_ARG;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     *out = ctx->rs;
-    return ERP_OK;
-}
-
-erp_status erp_rand_stream_shuffle_prefix(erp_rand_stream* s, int32_t m, int32_t n,
-                                          int32_t* h_idx) {
-    if (!s || m < 1 || n < 0 || n > m || (n > 0 && !h_idx)) return ERP_INVALID_ARG;
-    std::lock_guard<std::mutex> g(s->mu);
-    const erp_status es = rs_fetch(s);
-    if (es != ERP_OK) return es;
-    erp_shuffle_prefix_window(s->win, m, n, h_idx);  // (steps the window m - 1 draws)
-    s->draws += (uint64_t)(m - 1);
-    if (s->d_state) {  // (rs_fetch waited for the last device update; the lock keeps others out)
-        uint32_t h[erp::kStreamNextWin];
-        memcpy(h + erp::kStreamWin, s->win, sizeof(s->win));
-        h[erp::kStreamSeed] = s->seed;
-        memcpy(h + erp::kStreamDraws, &s->draws, 8);
-        ERP_CK(hipMemcpy(s->d_state, h, sizeof(h), hipMemcpyHostToDevice));
-        s->pending = false;
-    }
     return ERP_OK;
 }
 

@@ -1,6 +1,7 @@
 // erp_image_batch.hpp -- what the batched do_all (image_batch.hip) shares with the rotation
 // sweep (sweep.hip): the pack step over band features that need not lie pair after pair, the
-// argument checks of the packed outputs, the group budget and the context scratch slots.
+// argument checks of the packed outputs and the group budget.  (Their context scratch slots are
+// in erp_ctx.hpp's table.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,16 +18,6 @@ namespace erp {
 // of 64 (SURF's per-band cost grows with the bands per call), hence the cap.
 constexpr size_t kGroupBudgetBytes = (size_t)9 << 30;
 constexpr int32_t kMaxAutoGroupPairs = 8;
-
-// context scratch slots (capi.hip erp_ctx::extra): 13-17 the batched do_all's group (band
-// canvases, SURF's padded keypoints / descriptors / counts, the pack step's row bases), 18-24
-// the sweep's (the group's rotated images, the left image's keypoints / descriptors / counts,
-// the matched keypoints of erp_image_sweep_run's match error)
-enum {
-    kSlotBands = 13, kSlotKp = 14, kSlotDesc = 15, kSlotCount = 16, kSlotRowBase = 17,
-    kSlotSweepCanvas = 18, kSlotLeftKp = 19, kSlotLeftDesc = 20, kSlotLeftCount = 21,
-    kSlotSweepKeyL = 22, kSlotSweepKeyR = 23
-};
 
 // One side's band features as erp_surf_detect_compute_dev writes them -- kp [images][max_kp],
 // desc [images][max_kp][64], count [images] -- and where pair p's bands n0..n3 are among those

@@ -20,24 +20,14 @@
 #include <vector>
 
 #include "../../include/erp_match.h"
+#include "erp_ctx.hpp"
 #include "erp_device.hpp"
 #include "erp_image_batch.hpp"
 #include "erp_launch.hpp"
 #include "erp_remap.hpp"
 #include "erp_surf.hpp"
 
-int32_t erp_ctx_device_internal(erp_ctx* ctx);  // capi.hip
-void* erp_ctx_scratch_internal(erp_ctx* ctx, int which, size_t bytes);  // capi.hip (grow-only)
-void* erp_ctx_call_begin_internal(erp_ctx* ctx, hipStream_t st);
-void erp_ctx_call_end_internal(void* call);
-
 namespace {
-
-struct CtxCallGuard {
-    void* h;
-    CtxCallGuard(erp_ctx* c, hipStream_t st) : h(erp_ctx_call_begin_internal(c, st)) {}
-    ~CtxCallGuard() { erp_ctx_call_end_internal(h); }
-};
 
 constexpr int kPackRowsPerBlock = 16;  // 256 threads = 16 rows x 16 lanes of 16 B
 constexpr int kPackMaxBlocksPerBand = 16;
@@ -184,8 +174,7 @@ erp_status pack_enqueue(erp_ctx* ctx, const PackSide side[2], int32_t n_pairs, i
     a.o = out;
     a.s[0] = side[0];
     a.s[1] = side[1];
-    a.row_base = (int64_t*)erp_ctx_scratch_internal(ctx, kSlotRowBase,
-                                                    (size_t)n_pairs * 8 * sizeof(int64_t));
+    a.row_base = ctx_scratch<int64_t>(ctx, kSlotRowBase, (size_t)n_pairs * 8 * sizeof(int64_t));
     if (!a.row_base) return ERP_OUT_OF_MEMORY;
     a.n_pairs = n_pairs;
     a.max_kp = max_kp;
@@ -248,6 +237,8 @@ erp_status packed_batch_run(erp_ctx* ctx, const erp_packed_pairs& packed, int32_
 
 namespace {
 
+using erp::ctx_scratch;
+using erp::CtxCall;
 using erp::kSlotBands;
 using erp::kSlotCount;
 using erp::kSlotDesc;
@@ -273,8 +264,8 @@ erp_status features_checked(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* 
         !erp::surf_args_ok(W, H / 4, 3, prm, max_kp) || fill < 0 || fill > 255 ||
         max_group_pairs < 0 || !erp::packed_ok(out) || (n_pairs > 0 && (!d_left || !d_right)))
         return ERP_INVALID_ARG;
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
-    CtxCallGuard call(ctx, st);
+    if (hipSetDevice(ctx->device) != hipSuccess) return ERP_HIP_ERROR;
+    CtxCall call(ctx, st);
     if (n_pairs == 0) {
         if (hipMemsetAsync(out->off_l, 0, sizeof(int64_t), st) != hipSuccess ||
             hipMemsetAsync(out->off_r, 0, sizeof(int64_t), st) != hipSuccess)
@@ -294,12 +285,11 @@ erp_status features_checked(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* 
                           std::max<size_t>(erp::kGroupBudgetBytes / per_pair, 1),
                           (size_t)erp::kMaxAutoGroupPairs);
     g = std::min(g, n_pairs);
-    uint8_t* bands = (uint8_t*)erp_ctx_scratch_internal(ctx, kSlotBands, (size_t)g * 8 * band);
-    erp_keypoint* kp = (erp_keypoint*)erp_ctx_scratch_internal(
-        ctx, kSlotKp, (size_t)g * 8 * K * sizeof(erp_keypoint));
-    float* desc = (float*)erp_ctx_scratch_internal(ctx, kSlotDesc, (size_t)g * 8 * K * 64 * 4);
-    int32_t* cnt = (int32_t*)erp_ctx_scratch_internal(ctx, kSlotCount,
-                                                      (size_t)g * 8 * sizeof(int32_t));
+    uint8_t* bands = ctx_scratch<uint8_t>(ctx, kSlotBands, (size_t)g * 8 * band);
+    erp_keypoint* kp =
+        ctx_scratch<erp_keypoint>(ctx, kSlotKp, (size_t)g * 8 * K * sizeof(erp_keypoint));
+    float* desc = ctx_scratch<float>(ctx, kSlotDesc, (size_t)g * 8 * K * 64 * 4);
+    int32_t* cnt = ctx_scratch<int32_t>(ctx, kSlotCount, (size_t)g * 8 * sizeof(int32_t));
     if (!bands || !kp || !desc || !cnt) return ERP_OUT_OF_MEMORY;
     int32_t raw_max = 0;
     for (int32_t p0 = 0; p0 < n_pairs; p0 += g) {
@@ -336,9 +326,9 @@ erp_status erp_pack_band_features_dev(erp_ctx* ctx, const erp_keypoint* d_kp, co
         !erp::packed_ok(out) || (n_pairs > 0 && (!d_kp || !d_desc || !d_count)) ||
         ((uintptr_t)d_desc & 15) != 0)
         return ERP_INVALID_ARG;
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ERP_HIP_ERROR;
     hipStream_t st = (hipStream_t)stream;
-    CtxCallGuard call(ctx, st);
+    CtxCall call(ctx, st);
     if (n_pairs == 0)
         return hipMemsetAsync(out->off_l, 0, sizeof(int64_t), st) == hipSuccess &&
                        hipMemsetAsync(out->off_r, 0, sizeof(int64_t), st) == hipSuccess

@@ -11,13 +11,19 @@
 //
 // The same polynomial arithmetic on the host (glibc_poly_*) positions a stream that no GPU call
 // has used yet, and replaces the O(offset) loop of host_glibc_window for large offsets.
+//
+// The stream's host side is at the end of the file: the state's way to the device and back,
+// the process streams and the erp_rand_stream_* entry points of include/erp_match.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include <mutex>
+#include <new>
 #include <vector>
 
+#include "../../include/erp_match.h"
+#include "erp_ctx.hpp"
 #include "erp_jump_poly.hpp"
 #include "erp_kernels.hpp"
 #include "erp_launch.hpp"
@@ -327,4 +333,161 @@ hipError_t launch_stream_jump(uint32_t* state, int set, uint32_t seed, uint64_t 
     return hipGetLastError();
 }
 
+erp_status rs_to_device(erp_rand_stream* s, int device) {
+    std::lock_guard<std::mutex> g(s->mu);
+    if (s->d_state) return s->device == device ? ERP_OK : ERP_INVALID_ARG;
+    if (s->device >= 0 && s->device != device) return ERP_INVALID_ARG;  // a process stream
+    uint32_t h[kStreamStateWords] = {};
+    memcpy(h + kStreamWin, s->win, sizeof(s->win));
+    h[kStreamSeed] = s->seed;
+    memcpy(h + kStreamDraws, &s->draws, 8);
+    uint32_t* d = nullptr;
+    if (hipMalloc(&d, sizeof(h)) != hipSuccess) return ERP_OUT_OF_MEMORY;
+    hipEvent_t ev = nullptr;
+    if (hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
+        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        (void)hipFree(d);
+        return ERP_HIP_ERROR;
+    }
+    s->d_state = d;
+    s->ev = ev;
+    s->device = device;
+    return ERP_OK;
+}
+
 }  // namespace erp
+
+// ================================================= the stream's host side ===============
+// Small offsets step the recurrence; above kSeqOffsets the window before draw 0 is moved on by
+// x^offset mod P (glibc_poly_pow: ~128 products of 31 x 31 words whatever the offset).
+constexpr uint64_t kSeqOffsets = 4096;
+void host_glibc_window(uint32_t seed, uint64_t offset, uint32_t out[31]) {
+    if (offset <= kSeqOffsets) return erp::glibc_window_seq(seed, offset, out);
+    erp::glibc_window_seq(seed, 0, out);
+    erp::glibc_window_jump(out, offset);
+}
+
+namespace {
+
+// the stream's (seed, draws, window) on the host, after its last device update; s->mu held
+erp_status rs_fetch(erp_rand_stream* s) {
+    if (!s->d_state) return ERP_OK;
+    ERP_CK(hipSetDevice(s->device));
+    if (s->pending) ERP_CK(hipEventSynchronize(s->ev));
+    uint32_t h[erp::kStreamNextWin];
+    ERP_CK(hipMemcpy(h, s->d_state, sizeof(h), hipMemcpyDeviceToHost));
+    memcpy(s->win, h + erp::kStreamWin, sizeof(s->win));
+    s->seed = h[erp::kStreamSeed];
+    memcpy(&s->draws, h + erp::kStreamDraws, 8);
+    return ERP_OK;
+}
+
+// set (seed, offset) or advance by n; s->mu held.  Host arithmetic before the first device use,
+// one wave on the device after it (ordered by the stream's event, on the null stream)
+erp_status rs_jump(erp_rand_stream* s, bool set, uint32_t seed, uint64_t n) {
+    if (set && seed == 0) seed = 1;
+    if (!s->d_state) {
+        if (set) {
+            host_glibc_window(seed, n, s->win);
+            s->seed = seed;
+            s->draws = n;
+        } else {
+            erp::glibc_window_jump(s->win, n);
+            s->draws += n;
+        }
+        return ERP_OK;
+    }
+    ERP_CK(hipSetDevice(s->device));
+    if (s->pending) ERP_CK(hipStreamWaitEvent(nullptr, s->ev, 0));
+    ERP_CK(erp::launch_stream_jump(s->d_state, set ? 1 : 0, seed, n, nullptr));
+    ERP_CK(hipEventRecord(s->ev, nullptr));
+    s->pending = true;
+    return ERP_OK;
+}
+
+std::mutex g_process_mu;
+std::vector<erp_rand_stream*> g_process_streams;  // by device, never freed
+
+}  // namespace
+
+extern "C" {
+
+erp_status erp_rand_stream_create(uint32_t seed, uint64_t offset, erp_rand_stream** out) {
+    if (!out) return ERP_INVALID_ARG;
+    erp_rand_stream* s = new (std::nothrow) erp_rand_stream();
+    if (!s) return ERP_OUT_OF_MEMORY;
+    (void)rs_jump(s, true, seed, offset);
+    *out = s;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_destroy(erp_rand_stream* s) {
+    if (!s || s->process_owned) return ERP_INVALID_ARG;
+    if (s->d_state) {
+        (void)hipSetDevice(s->device);
+        if (s->pending) (void)hipEventSynchronize(s->ev);
+        (void)hipEventDestroy(s->ev);
+        (void)hipFree(s->d_state);
+    }
+    delete s;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_get(erp_rand_stream* s, uint32_t* seed, uint64_t* draws) {
+    if (!s) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    const erp_status es = rs_fetch(s);
+    if (es != ERP_OK) return es;
+    if (seed) *seed = s->seed;
+    if (draws) *draws = s->draws;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_set(erp_rand_stream* s, uint32_t seed, uint64_t offset) {
+    if (!s) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    return rs_jump(s, true, seed, offset);
+}
+
+erp_status erp_rand_stream_advance(erp_rand_stream* s, uint64_t n) {
+    if (!s) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    return rs_jump(s, false, 0, n);
+}
+
+erp_status erp_rand_stream_process(int32_t device, erp_rand_stream** out) {
+    if (!out || device < 0 || device >= 1024) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(g_process_mu);
+    if (g_process_streams.size() <= (size_t)device) g_process_streams.resize((size_t)device + 1);
+    erp_rand_stream*& s = g_process_streams[(size_t)device];
+    if (!s) {
+        s = new (std::nothrow) erp_rand_stream();
+        if (!s) return ERP_OUT_OF_MEMORY;
+        (void)rs_jump(s, true, 1, 0);
+        s->device = device;
+        s->process_owned = true;
+    }
+    *out = s;
+    return ERP_OK;
+}
+
+erp_status erp_rand_stream_shuffle_prefix(erp_rand_stream* s, int32_t m, int32_t n,
+                                          int32_t* h_idx) {
+    if (!s || m < 1 || n < 0 || n > m || (n > 0 && !h_idx)) return ERP_INVALID_ARG;
+    std::lock_guard<std::mutex> g(s->mu);
+    const erp_status es = rs_fetch(s);
+    if (es != ERP_OK) return es;
+    erp_shuffle_prefix_window(s->win, m, n, h_idx);  // (steps the window m - 1 draws)
+    s->draws += (uint64_t)(m - 1);
+    if (s->d_state) {  // (rs_fetch waited for the last device update; the lock keeps others out)
+        uint32_t h[erp::kStreamNextWin];
+        memcpy(h + erp::kStreamWin, s->win, sizeof(s->win));
+        h[erp::kStreamSeed] = s->seed;
+        memcpy(h + erp::kStreamDraws, &s->draws, 8);
+        ERP_CK(hipMemcpy(s->d_state, h, sizeof(h), hipMemcpyHostToDevice));
+        s->pending = false;
+    }
+    return ERP_OK;
+}
+
+}  // extern "C"

@@ -11,24 +11,13 @@
 #include <vector>
 
 #include "../../include/erp_match.h"
+#include "erp_ctx.hpp"
 #include "erp_device.hpp"
 #include "erp_remap.hpp"
 
-int32_t erp_ctx_device_internal(erp_ctx* ctx);  // capi.hip
-void* erp_ctx_scratch_internal(erp_ctx* ctx, int which, size_t bytes);  // capi.hip (grow-only)
-// capi.hip: the context's call section (lock + stream order after the previous call, whose
-// scratch this call reuses; records the end of this call's work on exit)
-void* erp_ctx_call_begin_internal(erp_ctx* ctx, hipStream_t st);
-void erp_ctx_call_end_internal(void* call);
 namespace {
-struct CtxCallGuard {
-    void* h;
-    CtxCallGuard(erp_ctx* c, hipStream_t st) : h(erp_ctx_call_begin_internal(c, st)) {}
-    ~CtxCallGuard() { erp_ctx_call_end_internal(h); }
-};
-}  // namespace
 
-namespace {
+using erp::CtxCall;
 
 // cv::gemm on 3x3 doubles: d[i][j] = (a[i][0] b[0][j] + a[i][1] b[1][j]) + a[i][2] b[2][j]
 void gemm33(const double* a, const double* b, double* d) {
@@ -46,15 +35,16 @@ double rad_f(float deg) { return (double)(float)(erp::kPi * (double)deg / 180.0)
 
 erp_status set_dev(erp_ctx* ctx) {
     if (!ctx) return ERP_INVALID_ARG;
-    return hipSetDevice(erp_ctx_device_internal(ctx)) == hipSuccess ? ERP_OK : ERP_HIP_ERROR;
+    return hipSetDevice(ctx->device) == hipSuccess ? ERP_OK : ERP_HIP_ERROR;
 }
 
 // the boundary list of a launch of up to kMaxRemapJobs jobs of `pixels` output pixels each
 bool scratch(erp_ctx* ctx, size_t pixels, erp::RemapScratch* scr) {
-    void* p = erp_ctx_scratch_internal(ctx, 0, 16 + pixels * erp::kMaxRemapJobs * 8);
+    char* p = erp::ctx_scratch<char>(ctx, erp::kSlotRemapList,
+                                     16 + pixels * erp::kMaxRemapJobs * 8);
     if (!p) return false;
     scr->count = (uint32_t*)p;
-    scr->list = (uint64_t*)((char*)p + 16);
+    scr->list = (uint64_t*)(p + 16);
     return true;
 }
 
@@ -77,7 +67,7 @@ bool fill_ok(int32_t fill) { return fill >= -1 && fill <= 255; }
 // -> W x H x 3, images and views contiguous in their stacks.  Route ERP_OPT_VERTICAL_SHARED: one
 // shared-map launch over every image (the matrix is the same for all of them), or ROT90 jobs of
 // launch_remap, kMaxRemapJobs per launch; the bytes are the same.  The boundary list of either
-// route lives in scratch slot 0 (the shared map's needs 4 bytes per pixel of the slot's 64).
+// route lives in kSlotRemapList (the shared map's needs 4 bytes per pixel of the slot's 64).
 erp_status vertical_enqueue(erp_ctx* ctx, const uint8_t* src, uint8_t* dst, const uint8_t* src2,
                             uint8_t* dst2, int32_t n, int32_t W, int32_t H, hipStream_t st) {
     if (n <= 0) return ERP_OK;
@@ -313,7 +303,7 @@ erp_status erp_crop_rotated_image_dev(erp_ctx* ctx, const uint8_t* d_im, int32_t
     if (!d_im || !d_out || !dims_ok(W, H) || H < 4) return ERP_INVALID_ARG;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     erp::RemapScratch scr;
     if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
     erp::RemapJobs jobs{};
@@ -334,7 +324,7 @@ erp_status erp_spherical_bands_dev(erp_ctx* ctx, const uint8_t* d_ims, int32_t n
         return ERP_INVALID_ARG;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     return erp::spherical_bands_enqueue(ctx, d_ims, n_images, W, H, d_bands,
                                         (size_t)4 * (H / 4) * W * 3, (hipStream_t)stream);
 }
@@ -344,7 +334,7 @@ erp_status erp_rotate_keypoints_dev(erp_ctx* ctx, erp_point2f* d_kp, int32_t n, 
     if (n < 0 || (n > 0 && !d_kp) || !dims_ok(W, H)) return ERP_INVALID_ARG;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     erp::BandKeypointArgs a{};
     for (int b = 0; b < 4; b++) {
         pitch_matrix(pitch_deg, a.m[b]);
@@ -369,7 +359,7 @@ erp_status erp_unrotate_band_keypoints_dev(erp_ctx* ctx, erp_point2f* d_kp,
     if (total > INT32_MAX || (total > 0 && !d_kp)) return ERP_INVALID_ARG;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     static const float pitch[4] = {45.f, 0.f, -45.f, -90.f};  // do_all :121-126
     erp::BandKeypointArgs a{};
     int32_t e = 0;
@@ -390,7 +380,7 @@ erp_status erp_rotate_image_dev(erp_ctx* ctx, const uint8_t* d_im, int32_t W, in
     if (!d_im || !d_out || !rot_mat || !dims_ok(W, H)) return ERP_INVALID_ARG;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     erp::RemapScratch scr;
     if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
     erp::RemapJobs jobs{};
@@ -412,7 +402,7 @@ erp_status erp_rectify_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d
         return ERP_INVALID_ARG;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     erp::RemapScratch scr;
     if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
     erp::RemapJobs jobs{};
@@ -435,7 +425,7 @@ erp_status erp_vertical_rotate_dev(erp_ctx* ctx, const uint8_t* d_im, int32_t W,
     if (!d_im || !d_out || !dims_ok(W, H)) return ERP_INVALID_ARG;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     erp::RemapScratch scr;
     if (!scratch(ctx, (size_t)W * H, &scr)) return ERP_OUT_OF_MEMORY;
     erp::RemapJobs jobs{};
@@ -458,7 +448,7 @@ erp_status erp_vertical_rotate_batch_dev(erp_ctx* ctx, const uint8_t* d_ims, int
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
     hipStream_t st = (hipStream_t)stream;
-    CtxCallGuard call(ctx, st);
+    CtxCall call(ctx, st);
     if (!prefill(d_out, fill, (size_t)n * W * H * 3, st)) return ERP_HIP_ERROR;
     return vertical_enqueue(ctx, d_ims, d_out, nullptr, nullptr, n, W, H, st);
 }
@@ -479,7 +469,7 @@ erp_status erp_rectify_batch_dev(erp_ctx* ctx, const uint8_t* d_left, const uint
                                      &m[(size_t)p * 9], &m[(size_t)(n_pairs + p) * 9]) == ERP_OK;
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
-    CtxCallGuard call(ctx, (hipStream_t)stream);
+    CtxCall call(ctx, (hipStream_t)stream);
     return rectify_batch_enqueue(ctx, d_left, d_right, n_pairs, W, H, m.data(),
                                  m.data() + (size_t)n_pairs * 9, ok.data(), fill, *outputs,
                                  (hipStream_t)stream);
@@ -510,7 +500,7 @@ erp_status erp_rectify_results_dev(erp_ctx* ctx, const uint8_t* d_left, const ui
     erp_status s = set_dev(ctx);
     if (s != ERP_OK) return s;
     hipStream_t st = (hipStream_t)stream;
-    CtxCallGuard call(ctx, st);
+    CtxCall call(ctx, st);
     std::vector<erp_pair_result> rec(n_pairs);
     if (hipMemcpyAsync(rec.data(), d_results, rec.size() * sizeof(erp_pair_result),
                        hipMemcpyDeviceToHost, st) != hipSuccess ||

@@ -11,22 +11,8 @@
 #include <vector>
 
 #include "../../include/erp_match.h"
+#include "erp_ctx.hpp"
 #include "erp_surf.hpp"
-
-int32_t erp_ctx_device_internal(erp_ctx* ctx);
-void* erp_ctx_scratch_internal(erp_ctx* ctx, int which, size_t bytes);
-// capi.hip: the context's call section (lock + stream order after the previous call, whose
-// scratch this call reuses; records the end of this call's work on exit)
-void* erp_ctx_call_begin_internal(erp_ctx* ctx, hipStream_t st);
-void erp_ctx_call_end_internal(void* call);
-namespace {
-struct CtxCallGuard {
-    void* h;
-    CtxCallGuard(erp_ctx* c, hipStream_t st) : h(erp_ctx_call_begin_internal(c, st)) {}
-    ~CtxCallGuard() { erp_ctx_call_end_internal(h); }
-};
-}  // namespace
-uint64_t* erp_ctx_surf_key_internal(erp_ctx* ctx);
 
 namespace {
 
@@ -191,35 +177,34 @@ erp_status surf_detect_compute_enqueue(erp_ctx* ctx, const uint8_t* d_images, in
         if (n != erp::kSurfNOri) return ERP_INTERNAL;
         gaussian(20, 3.3, plan.consts.gdesc);
     }
-    // the table on the device (slot 1), uploaded when (W, H, params) change
+    // the table on the device, uploaded when (W, H, params) change
     const size_t tbytes = sizeof(erp::SurfLayer) * nT + sizeof(int) * mid.size();
-    char* tab = (char*)erp_ctx_scratch_internal(ctx, 1, tbytes);
+    char* tab = ctx_scratch<char>(ctx, kSlotSurfLayers, tbytes);
     if (!tab) return ERP_OUT_OF_MEMORY;
     uint64_t key = 1469598103934665603ull;
     auto mix = [&](uint64_t v) { key = (key ^ v) * 1099511628211ull; };
     mix((uint64_t)W); mix((uint64_t)H); mix((uint64_t)nO); mix((uint64_t)nL);
     mix((uint64_t)(uintptr_t)tab);
-    uint64_t* cached = erp_ctx_surf_key_internal(ctx);
-    if (*cached != key) {
+    if (ctx->surf_key != key) {
         std::vector<char> host(tbytes);
         memcpy(host.data(), layers.data(), sizeof(erp::SurfLayer) * nT);
         memcpy(host.data() + sizeof(erp::SurfLayer) * nT, mid.data(), sizeof(int) * mid.size());
         if (hipMemcpyAsync(tab, host.data(), tbytes, hipMemcpyHostToDevice, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             return ERP_HIP_ERROR;
-        *cached = key;
+        ctx->surf_key = key;
     }
     plan.d_layers = (const erp::SurfLayer*)tab;
     plan.d_mid = (const int*)(tab + sizeof(erp::SurfLayer) * nT);
     // scratch
     erp::SurfScratch scr{};
     const size_t n = (size_t)n_images, K = (size_t)max_kp;
-    scr.gray = (uint8_t*)erp_ctx_scratch_internal(ctx, 2, channels == 3 ? n * W * H : 16);
-    scr.sum = (int32_t*)erp_ctx_scratch_internal(ctx, 3, n * (W + 1) * (H + 1) * 4);
-    scr.det = (float*)erp_ctx_scratch_internal(ctx, 4, n * plan.det_per_img * 4);
-    scr.raw = (erp_keypoint*)erp_ctx_scratch_internal(ctx, 5, n * K * sizeof(erp_keypoint));
-    scr.sorted = (erp_keypoint*)erp_ctx_scratch_internal(ctx, 6, n * K * sizeof(erp_keypoint));
-    scr.desc = (float*)erp_ctx_scratch_internal(ctx, 7, n * K * 64 * 4);
+    scr.gray = ctx_scratch<uint8_t>(ctx, kSlotSurfGray, channels == 3 ? n * W * H : 16);
+    scr.sum = ctx_scratch<int32_t>(ctx, kSlotSurfSum, n * (W + 1) * (H + 1) * 4);
+    scr.det = ctx_scratch<float>(ctx, kSlotSurfDet, n * plan.det_per_img * 4);
+    scr.raw = ctx_scratch<erp_keypoint>(ctx, kSlotSurfRaw, n * K * sizeof(erp_keypoint));
+    scr.sorted = ctx_scratch<erp_keypoint>(ctx, kSlotSurfSorted, n * K * sizeof(erp_keypoint));
+    scr.desc = ctx_scratch<float>(ctx, kSlotSurfDesc, n * K * 64 * 4);
     if (!scr.gray || !scr.sum || !scr.det || !scr.raw || !scr.sorted || !scr.desc)
         return ERP_OUT_OF_MEMORY;
     if (erp::launch_surf_detect(d_images, n_images, W, H, channels, plan, scr, max_kp, d_count, st) !=
@@ -242,10 +227,10 @@ erp_status surf_detect_compute_enqueue(erp_ctx* ctx, const uint8_t* d_images, in
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(total, 1),
                                                                  ((size_t)1 << 30) / (scr.slot * 4)));
     const int nbands = (max_win + erp::surf_band_rows() - 1) / erp::surf_band_rows();
-    scr.pool = (float*)erp_ctx_scratch_internal(ctx, 8, (size_t)chunk * scr.slot * 4);
-    scr.jobs = (erp::SurfJob*)erp_ctx_scratch_internal(ctx, 9, (size_t)chunk * erp::surf_job_bytes());
-    scr.items = (int2*)erp_ctx_scratch_internal(ctx, 10, (size_t)chunk * nbands * sizeof(int2));
-    int32_t* dk = (int32_t*)erp_ctx_scratch_internal(ctx, 11, (n + 1 + 16) * sizeof(int32_t));
+    scr.pool = ctx_scratch<float>(ctx, kSlotSurfPool, (size_t)chunk * scr.slot * 4);
+    scr.jobs = ctx_scratch<erp::SurfJob>(ctx, kSlotSurfJobs, (size_t)chunk * erp::surf_job_bytes());
+    scr.items = ctx_scratch<int2>(ctx, kSlotSurfItems, (size_t)chunk * nbands * sizeof(int2));
+    int32_t* dk = ctx_scratch<int32_t>(ctx, kSlotSurfKpre, (n + 1 + 16) * sizeof(int32_t));
     if (!scr.pool || !scr.jobs || !scr.items || !dk) return ERP_OUT_OF_MEMORY;
     scr.nitems = dk + n + 1;
     if (total > 0) {
@@ -284,9 +269,9 @@ erp_status erp_surf_detect_compute_dev(erp_ctx* ctx, const uint8_t* d_images, in
         return ERP_INVALID_ARG;
     if (n_images == 0) return ERP_OK;
     if (!d_images || !d_kp || !d_desc || !d_count) return ERP_INVALID_ARG;
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ERP_HIP_ERROR;
     hipStream_t st = (hipStream_t)stream;
-    CtxCallGuard call(ctx, st);
+    erp::CtxCall call(ctx, st);
     return erp::surf_detect_compute_enqueue(ctx, d_images, n_images, W, H, channels, prm, max_kp,
                                             d_kp, d_desc, d_count, st, nullptr);
 }

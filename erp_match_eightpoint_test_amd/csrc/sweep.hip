@@ -23,24 +23,17 @@
 #include <vector>
 
 #include "../../include/erp_match.h"
+#include "erp_ctx.hpp"
 #include "erp_device.hpp"
 #include "erp_image_batch.hpp"
 #include "erp_launch.hpp"
 #include "erp_remap.hpp"
 #include "erp_surf.hpp"
 
-int32_t erp_ctx_device_internal(erp_ctx* ctx);  // capi.hip
-void* erp_ctx_scratch_internal(erp_ctx* ctx, int which, size_t bytes);  // capi.hip (grow-only)
-void* erp_ctx_call_begin_internal(erp_ctx* ctx, hipStream_t st);
-void erp_ctx_call_end_internal(void* call);
-
 namespace {
 
-struct CtxCallGuard {
-    void* h;
-    CtxCallGuard(erp_ctx* c, hipStream_t st) : h(erp_ctx_call_begin_internal(c, st)) {}
-    ~CtxCallGuard() { erp_ctx_call_end_internal(h); }
-};
+using erp::ctx_scratch;
+using erp::CtxCall;
 
 // ---- the match error (one_image_test/main.cpp:27-50, :115-129) ----
 constexpr int kMePairsPerLaunch = 32;  // poses per launch: their matrices travel as kernel
@@ -168,8 +161,8 @@ erp_status sweep_features_checked(erp_ctx* ctx, const uint8_t* d_left, const uin
         return ERP_INVALID_ARG;
     std::vector<double> mats;
     if (!pose_matrices(h_rot_mat, n_poses, &mats)) return ERP_INVALID_ARG;  // before any GPU work
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
-    CtxCallGuard call(ctx, st);
+    if (hipSetDevice(ctx->device) != hipSuccess) return ERP_HIP_ERROR;
+    CtxCall call(ctx, st);
     if (n_poses == 0) {
         if (hipMemsetAsync(out->off_l, 0, sizeof(int64_t), st) != hipSuccess ||
             hipMemsetAsync(out->off_r, 0, sizeof(int64_t), st) != hipSuccess)
@@ -194,17 +187,16 @@ erp_status sweep_features_checked(erp_ctx* ctx, const uint8_t* d_left, const uin
                                                 (size_t)erp::kMaxAutoGroupPairs);
     g = std::min(g, n_poses);
     // the band canvases hold the left image's four bands first, then each group's 4 g
-    uint8_t* bands = (uint8_t*)erp_ctx_scratch_internal(ctx, erp::kSlotBands, (size_t)g * 4 * band);
-    uint8_t* canvas = (uint8_t*)erp_ctx_scratch_internal(ctx, erp::kSlotSweepCanvas, (size_t)g * img);
-    erp_keypoint* kp = (erp_keypoint*)erp_ctx_scratch_internal(
-        ctx, erp::kSlotKp, (size_t)g * 4 * K * sizeof(erp_keypoint));
-    float* desc = (float*)erp_ctx_scratch_internal(ctx, erp::kSlotDesc, (size_t)g * 4 * K * 64 * 4);
-    int32_t* cnt = (int32_t*)erp_ctx_scratch_internal(ctx, erp::kSlotCount,
-                                                      (size_t)g * 4 * sizeof(int32_t));
-    erp_keypoint* lkp = (erp_keypoint*)erp_ctx_scratch_internal(ctx, erp::kSlotLeftKp,
-                                                                4 * K * sizeof(erp_keypoint));
-    float* ldesc = (float*)erp_ctx_scratch_internal(ctx, erp::kSlotLeftDesc, 4 * K * 64 * 4);
-    int32_t* lcnt = (int32_t*)erp_ctx_scratch_internal(ctx, erp::kSlotLeftCount, 4 * sizeof(int32_t));
+    uint8_t* bands = ctx_scratch<uint8_t>(ctx, erp::kSlotBands, (size_t)g * 4 * band);
+    uint8_t* canvas = ctx_scratch<uint8_t>(ctx, erp::kSlotSweepCanvas, (size_t)g * img);
+    erp_keypoint* kp =
+        ctx_scratch<erp_keypoint>(ctx, erp::kSlotKp, (size_t)g * 4 * K * sizeof(erp_keypoint));
+    float* desc = ctx_scratch<float>(ctx, erp::kSlotDesc, (size_t)g * 4 * K * 64 * 4);
+    int32_t* cnt = ctx_scratch<int32_t>(ctx, erp::kSlotCount, (size_t)g * 4 * sizeof(int32_t));
+    erp_keypoint* lkp =
+        ctx_scratch<erp_keypoint>(ctx, erp::kSlotLeftKp, 4 * K * sizeof(erp_keypoint));
+    float* ldesc = ctx_scratch<float>(ctx, erp::kSlotLeftDesc, 4 * K * 64 * 4);
+    int32_t* lcnt = ctx_scratch<int32_t>(ctx, erp::kSlotLeftCount, 4 * sizeof(int32_t));
     if (!bands || !canvas || !kp || !desc || !cnt || !lkp || !ldesc || !lcnt)
         return ERP_OUT_OF_MEMORY;
     int32_t raw_max = 0;
@@ -251,9 +243,9 @@ erp_status erp_match_error_dev(erp_ctx* ctx, const erp_point2f* d_key_left,
                                      h_rot_mat, W, H, d_out))
         return ERP_INVALID_ARG;
     if (n_pairs == 0) return ERP_OK;
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ERP_HIP_ERROR;
     hipStream_t st = (hipStream_t)stream;
-    CtxCallGuard call(ctx, st);
+    CtxCall call(ctx, st);
     return match_error_enqueue(d_key_left, d_key_right, key_stride, d_m, m_stride, n_pairs,
                                h_rot_mat, W, H, d_out, st);
 }
@@ -287,14 +279,14 @@ erp_status erp_image_sweep_run(erp_ctx* ctx, const uint8_t* d_left, const uint8_
         // the matched keypoints the match error reads: the caller's where given, else scratch
         const size_t kb = (size_t)n_poses * (size_t)std::max(info->max_nq, 1) * sizeof(erp_point2f);
         if (!o.key_left)
-            o.key_left = (erp_point2f*)erp_ctx_scratch_internal(ctx, erp::kSlotSweepKeyL, kb);
+            o.key_left = ctx_scratch<erp_point2f>(ctx, erp::kSlotSweepKeyL, kb);
         if (!o.key_right)
-            o.key_right = (erp_point2f*)erp_ctx_scratch_internal(ctx, erp::kSlotSweepKeyR, kb);
+            o.key_right = ctx_scratch<erp_point2f>(ctx, erp::kSlotSweepKeyR, kb);
         if (!o.key_left || !o.key_right) return ERP_OUT_OF_MEMORY;
     }
     s = erp::packed_batch_run(ctx, *packed, n_poses, *info, ratio, cfg, &o, st);
     if (s != ERP_OK || !d_match_error) return s;
-    CtxCallGuard call(ctx, st);
+    CtxCall call(ctx, st);
     return match_error_enqueue(o.key_left, o.key_right, info->max_nq, &out->results[0].M,
                                (int64_t)(sizeof(erp_pair_result) / sizeof(int32_t)), n_poses,
                                h_rot_mat, W, H, d_match_error, st);

@@ -19,14 +19,8 @@
 #include <vector>
 
 #include "../../include/erp_match.h"
+#include "erp_ctx.hpp"
 #include "erp_launch.hpp"
-
-int32_t erp_ctx_device_internal(erp_ctx* ctx);                          // capi.hip
-void* erp_ctx_stamp_buffer_internal(erp_ctx* ctx, size_t bytes, uint32_t* epoch, bool* fresh);
-void* erp_ctx_call_begin_internal(erp_ctx* ctx, hipStream_t st);
-void erp_ctx_call_end_internal(void* call);
-void host_glibc_window(uint32_t seed, uint64_t offset, uint32_t out[31]);  // capi.hip
-erp_rand_stream* erp_ctx_rand_stream_internal(erp_ctx* ctx);               // capi.hip
 
 namespace erp {
 namespace {
@@ -273,18 +267,29 @@ __global__ __launch_bounds__(256) void draw_match_kernel(const uint8_t* __restri
     }
 }
 
-struct CallGuard {
-    void* h;
-    CallGuard(erp_ctx* c, hipStream_t st) : h(erp_ctx_call_begin_internal(c, st)) {}
-    ~CallGuard() { erp_ctx_call_end_internal(h); }
-};
+// the draw_match line buffer: grown like the other slots, with a per-call epoch for its stamps
+// (epoch << 16 | match index); *fresh = the buffer must be zeroed first (new memory, or the
+// 16-bit epoch wrapped)
+uint32_t* stamp_buffer(erp_ctx* ctx, size_t bytes, uint32_t* epoch, bool* fresh) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    // growth is detected by the size: hipMalloc may hand the freed address back for the larger
+    // block, whose tail then holds stale stamps
+    const size_t n_before = ctx->extra[kSlotVizStamps].n;
+    uint32_t* win = ctx_scratch<uint32_t>(ctx, kSlotVizStamps, bytes);
+    if (!win) return nullptr;
+    *fresh = ctx->extra[kSlotVizStamps].n != n_before || ctx->viz_epoch == 0 ||
+             ctx->viz_epoch >= 0xFFFFu;
+    ctx->viz_epoch = *fresh ? 1u : ctx->viz_epoch + 1u;
+    *epoch = ctx->viz_epoch;
+    return win;
+}
 
 }  // namespace
 }  // namespace erp
 
 // iota + std::random_shuffle (libstdc++: rand() % (i + 1) for i = 1 .. m-1) on the glibc window
 // `ring` (r[n-31..n-1]); the first n entries into h_idx.  On return ring is the window m - 1
-// draws further on.  (global linkage: the rand stream's shuffle in capi.hip)
+// draws further on.
 void erp_shuffle_prefix_window(uint32_t ring[31], int32_t m, int32_t n, int32_t* h_idx) {
     int pos = 0;  // ring[pos] = r[n-31]
     auto rnd = [&]() {
@@ -326,13 +331,13 @@ erp_status erp_epipolar_draw_dev(erp_ctx* ctx, const erp_point2f* h_key_left,
         im_width < 1 || im_height < 1 || out_width < 1 || out_height < 1 || !h_key_left ||
         !h_key_right || (int64_t)out_width * out_height > ((int64_t)1 << 30))
         return ERP_INVALID_ARG;
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ERP_HIP_ERROR;
     const hipStream_t st = (hipStream_t)stream;
-    CallGuard call(ctx, st);
+    CtxCall call(ctx, st);
     // iota + std::random_shuffle on the glibc rand() stream (src/epipolar_tool.cpp:13-16)
     int32_t idx[kEpiMaxKeys];
     // (a context with a rand stream draws from it, and advances it, whatever seed / offset say)
-    if (erp_rand_stream* rs = erp_ctx_rand_stream_internal(ctx)) {
+    if (erp_rand_stream* rs = ctx->rs) {
         const erp_status ss = erp_rand_stream_shuffle_prefix(rs, m, n_key, idx);
         if (ss != ERP_OK) return ss;
     } else if (n_key > 0) {
@@ -378,14 +383,13 @@ erp_status erp_draw_match_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t
         (m > 0 && (!d_key_left || !d_key_right)) || (int64_t)W * H > ((int64_t)1 << 30) ||
         (((uintptr_t)d_left | (uintptr_t)d_right | (uintptr_t)d_out) & 3))
         return ERP_INVALID_ARG;
-    if (hipSetDevice(erp_ctx_device_internal(ctx)) != hipSuccess) return ERP_HIP_ERROR;
+    if (hipSetDevice(ctx->device) != hipSuccess) return ERP_HIP_ERROR;
     const hipStream_t st = (hipStream_t)stream;
-    CallGuard call(ctx, st);
+    CtxCall call(ctx, st);
     const int64_t npix = (int64_t)W * H;
     uint32_t epoch = 0;
     bool fresh = false;
-    auto* win = (uint32_t*)erp_ctx_stamp_buffer_internal(ctx, (size_t)(npix + 4) * 4, &epoch,
-                                                         &fresh);
+    uint32_t* win = stamp_buffer(ctx, (size_t)(npix + 4) * 4, &epoch, &fresh);
     if (!win) return ERP_OUT_OF_MEMORY;
     if (fresh && hipMemsetAsync(win, 0, (size_t)(npix + 4) * 4, st) != hipSuccess)
         return ERP_HIP_ERROR;
