@@ -26,13 +26,14 @@ import ctypes as C
 import numpy as np
 
 from . import capi, synth
-from .capi import (DMATCH_DTYPE, HYP_DTYPE, RESULT_DTYPE, Context, ErpError, RandStream, check,
-                   default_cfg, process_rand_stream)
+from .capi import (DMATCH_DTYPE, HYP_DTYPE, POLISH_DTYPE, POLISH_ROUND_DTYPE, RESULT_DTYPE, Context,
+                   ErpError, RandStream, check, default_cfg, process_rand_stream)
 
 __all__ = ["feature_matcher", "eight_point", "erp_rotation", "spherical_surf", "epipolar_tool",
            "PairBatchRunner", "Context", "ErpError", "RandStream", "process_rand_stream",
-           "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "results_to_numpy",
-           "hyps_to_numpy", "sweep_relative_rotation", "synth", "capi"]
+           "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "POLISH_DTYPE",
+           "POLISH_ROUND_DTYPE", "results_to_numpy", "hyps_to_numpy", "polish_to_numpy",
+           "polish_rounds_to_numpy", "sweep_relative_rotation", "synth", "capi"]
 
 
 def _np_ptr(a: np.ndarray):
@@ -173,6 +174,7 @@ class eight_point:  # noqa: N801  (reference class name)
         self.ctx = ctx or Context(device)
         self.cfg = default_cfg(**cfg)
         self.last_result = None
+        self.last_polish = None
         if stream is not None:
             self.ctx.set_rand_stream(stream)
 
@@ -195,6 +197,31 @@ class eight_point:  # noqa: N801  (reference class name)
         self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
         check(st, "find")
         return R, T
+
+    def find_polished(self, im_width: int, im_height: int, key_left, key_right, thr: float,
+                      rounds: int = 3, match_size: int | None = None):
+        """find followed by the polish stage (erp_eight_point_find_polished; no reference
+        counterpart): the winner's inliers under |l^T E' r| < thr and up to ``rounds`` refits on
+        them -> (R (3,), T (3,), inlier_mask (match_size,) bool) of the last accepted state.
+        ``last_result`` is find's record (its R, T are find's answer), ``last_polish`` the
+        polish record (POLISH_DTYPE).  Consumes a rand stream exactly as find does."""
+        kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
+        kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
+        m = kl.shape[0] if match_size is None else int(match_size)
+        if m > kl.shape[0] or m > kr.shape[0]:
+            raise ValueError("match_size larger than the keypoint arrays")
+        kl = np.ascontiguousarray(kl[:m])
+        kr = np.ascontiguousarray(kr[:m])
+        res, pol = capi.PairResult(), capi.PolishResult()
+        mask = np.zeros(max(m, 1), np.uint8)
+        st = self.ctx.L.erp_eight_point_find_polished(self.ctx.h, im_width, im_height, _np_ptr(kl),
+                                                      _np_ptr(kr), m, C.byref(self.cfg), thr,
+                                                      int(rounds), C.byref(res), C.byref(pol),
+                                                      _np_ptr(mask))
+        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
+        self.last_polish = np.frombuffer(bytes(pol), POLISH_DTYPE)[0]
+        check(st, "find_polished")
+        return self.last_polish["R"].copy(), self.last_polish["T"].copy(), mask[:m].astype(bool)
 
     def initial_guess(self, im_width: int, im_height: int, key_point_left_rect,
                       key_point_right_rect, match_size: int | None = None):
@@ -994,6 +1021,22 @@ class PairBatchRunner:
             out["match_error"] = err[:n]
         return out
 
+    def polish(self, out: dict, width, height, thr: float, rounds: int = 3,
+               want_rounds: bool = False, stream=None) -> dict:
+        """The polish stage (include/erp_match.h "polish"; no reference counterpart) on the dict
+        ``run(..., want=("hyps", "key_left", "key_right"))`` returned: the inlier set of every
+        pair's winner under |l^T E' r| < thr and up to ``rounds`` refits on it -> {"polish":
+        records (polish_to_numpy), "mask": uint8 [P, max_nq] (1 = inlier of the final state),
+        "rounds": the per-round records (want_rounds; polish_rounds_to_numpy)}.  One launch on
+        torch's current stream (or ``stream``), nothing leaves the device; ``out`` is only read."""
+        missing = [k for k in ("results", "hyps", "key_left", "key_right") if k not in out]
+        if missing:
+            raise ValueError(f"polish needs run(..., want=('hyps', 'key_left', 'key_right')): "
+                             f"missing {missing}")
+        return self.ctx.polish(out["results"], out["hyps"], out["key_left"], out["key_right"],
+                               width, height, thr, rounds=rounds, valid_abs=self.cfg.valid_abs,
+                               want_rounds=want_rounds, stream=stream)
+
     def _launch(self, b, ratio, outs, stream, dev):
         import torch
         o = capi.BatchOutputs(*[outs[k].data_ptr() if k in outs else None
@@ -1007,6 +1050,17 @@ class PairBatchRunner:
 
 def results_to_numpy(t) -> np.ndarray:
     return t.cpu().numpy().view(RESULT_DTYPE).reshape(-1)
+
+
+def polish_to_numpy(t) -> np.ndarray:
+    """erp_polish_result records (Context.polish / PairBatchRunner.polish "polish") -> [P]"""
+    return t.cpu().numpy().view(POLISH_DTYPE).reshape(-1)
+
+
+def polish_rounds_to_numpy(t) -> np.ndarray:
+    """erp_polish_round records ("rounds") -> [P, rounds]"""
+    a = t.cpu().numpy()
+    return a.reshape(a.shape[0], -1).view(POLISH_ROUND_DTYPE)
 
 
 def hyps_to_numpy(t) -> np.ndarray:

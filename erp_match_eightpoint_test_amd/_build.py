@@ -19,7 +19,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("ERP_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip", "surf.hip", "surf_api.hip", "viz.hip",
-           "image_batch.hip", "rand_stream.hip", "sweep.hip",
+           "image_batch.hip", "rand_stream.hip", "sweep.hip", "polish.hip",
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
            "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp", "erp_ctx.hpp"]
@@ -112,6 +112,9 @@ DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "class_api_driver")
 # two successive erp::eight_point objects on erp::rand_stream::process()
 STREAM_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "rand_stream_driver.cpp")
 STREAM_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "rand_stream_driver")
+# erp::eight_point::find_polished
+POLISH_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "polish_driver.cpp")
+POLISH_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "polish_driver")
 
 
 def _build_cpp_driver(src: str, out: str, force: bool) -> str:
@@ -128,13 +131,18 @@ def _build_cpp_driver(src: str, out: str, force: bool) -> str:
 def build_driver(force: bool = False) -> str:
     """the C++ class-API drivers (tests/cpp): host code only, g++ against liberp_match.so -- the
     link a reference maintainer would do.  Returns the class API
-    driver; build_stream_driver() the rand stream one."""
+    driver; build_stream_driver() the rand stream one, build_polish_driver() the polish one."""
     _build_cpp_driver(STREAM_DRIVER_SRC, STREAM_DRIVER_BIN, force)
+    _build_cpp_driver(POLISH_DRIVER_SRC, POLISH_DRIVER_BIN, force)
     return _build_cpp_driver(DRIVER_SRC, DRIVER_BIN, force)
 
 
 def build_stream_driver(force: bool = False) -> str:
     return _build_cpp_driver(STREAM_DRIVER_SRC, STREAM_DRIVER_BIN, force)
+
+
+def build_polish_driver(force: bool = False) -> str:
+    return _build_cpp_driver(POLISH_DRIVER_SRC, POLISH_DRIVER_BIN, force)
 
 
 if __name__ == "__main__":

@@ -67,6 +67,25 @@ class BatchOutputs(C.Structure):
                 ("samples", P), ("rvec", P), ("tvec", P), ("dist", P)]
 
 
+class PolishRound(C.Structure):
+    _fields_ = [("R", C.c_float * 3), ("T", C.c_float * 3), ("n_fit", C.c_int32),
+                ("n_inliers", C.c_int32), ("which", C.c_int32), ("reserved", C.c_int32),
+                ("E", C.c_double * 9)]
+
+
+class PolishResult(C.Structure):
+    _fields_ = [("R", C.c_float * 3), ("T", C.c_float * 3), ("status", C.c_int32),
+                ("winner_iter", C.c_int32), ("winner_which", C.c_int32),
+                ("rounds_done", C.c_int32), ("n_inliers", C.c_int32),
+                ("n_inliers_winner", C.c_int32), ("E", C.c_double * 9)]
+
+
+class PolishInputs(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("iters", C.c_int32), ("key_stride", C.c_int64),
+                ("key_left", P), ("key_right", P), ("width", P), ("height", P), ("results", P),
+                ("hyps", P)]
+
+
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"),
                          ("distance", "<f4")])
 HYP_DTYPE = np.dtype([("R1", "<f4", 3), ("R2", "<f4", 3), ("T", "<f4", 3), ("R1_valid", "<i4"),
@@ -75,7 +94,18 @@ RESULT_DTYPE = np.dtype([("R", "<f4", 3), ("T", "<f4", 3), ("status", "<i4"), ("
                          ("K", "<i4"), ("min_idx", "<i4"), ("sample_n", "<i4"),
                          ("near_ties", "<i4"), ("survivors", "<i4"), ("binned_rows", "<i4"),
                          ("min_dist", "<f8")], align=True)
+POLISH_ROUND_DTYPE = np.dtype([("R", "<f4", 3), ("T", "<f4", 3), ("n_fit", "<i4"),
+                               ("n_inliers", "<i4"), ("which", "<i4"), ("reserved", "<i4"),
+                               ("E", "<f8", 9)], align=True)
+POLISH_DTYPE = np.dtype([("R", "<f4", 3), ("T", "<f4", 3), ("status", "<i4"),
+                         ("winner_iter", "<i4"), ("winner_which", "<i4"), ("rounds_done", "<i4"),
+                         ("n_inliers", "<i4"), ("n_inliers_winner", "<i4"), ("E", "<f8", 9)],
+                        align=True)
+POLISH_MAX_ROUNDS = 8
 assert DMATCH_DTYPE.itemsize == C.sizeof(DMatch) == 16
+assert POLISH_ROUND_DTYPE.itemsize == C.sizeof(PolishRound) == 112
+assert POLISH_DTYPE.itemsize == C.sizeof(PolishResult) == 120
+assert C.sizeof(PolishInputs) == 64
 assert HYP_DTYPE.itemsize == C.sizeof(Hypothesis) == 120
 assert RESULT_DTYPE.itemsize == C.sizeof(PairResult) == 64
 assert C.sizeof(RansacCfg) == 56
@@ -102,7 +132,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_ctx_set_rand_stream", "erp_ctx_get_rand_stream",
             "erp_rand_stream_shuffle_prefix", "erp_image_sweep_features_dev",
             "erp_image_sweep_run", "erp_match_error_dev", "erp_vertical_rotate_batch_dev",
-            "erp_rectify_batch_dev", "erp_rectify_results_dev", "erp_rectify_matrices_results"]
+            "erp_rectify_batch_dev", "erp_rectify_results_dev", "erp_rectify_matrices_results",
+            "erp_polish_dev", "erp_eight_point_find_polished"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -272,6 +303,11 @@ def load(build_if_missing: bool = False):
     L.erp_ctx_set_rand_stream.argtypes = [P, P]
     L.erp_ctx_get_rand_stream.argtypes = [P, C.POINTER(P)]
     L.erp_rand_stream_shuffle_prefix.argtypes = [P, C.c_int32, C.c_int32, P]
+    L.erp_polish_dev.argtypes = [P, C.POINTER(PolishInputs), C.c_double, C.c_float, C.c_int32, P,
+                                 P, P, P]
+    L.erp_eight_point_find_polished.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
+                                                C.POINTER(RansacCfg), C.c_float, C.c_int32, P, P,
+                                                P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]
@@ -388,6 +424,47 @@ class Context:
         check(self.L.erp_ctx_set_rand_stream(self.h, stream.h if stream is not None else None),
               "set_rand_stream")
         self.rand_stream = stream
+
+    def polish(self, results, hyps, key_left, key_right, width, height, thr: float,
+               rounds: int = 3, valid_abs: float = 1.57, want_rounds: bool = False,
+               want_mask: bool = True, stream=None) -> dict:
+        """erp_polish_dev on torch CUDA tensors: results [P, 64] uint8, hyps [P, iters, 120]
+        uint8, key_left / key_right [P, stride, 2] float32, width / height [P] int32 -> {"polish":
+        uint8 [P, 120] (POLISH_DTYPE), "rounds": uint8 [P, rounds, 112] (want_rounds), "mask":
+        uint8 [P, stride] (want_mask)}.  Asynchronous on ``stream`` (default: torch's current
+        stream); valid_abs = the cfg.valid_abs of the call that wrote the records."""
+        import torch
+        for t, dt in ((results, torch.uint8), (hyps, torch.uint8), (key_left, torch.float32),
+                      (key_right, torch.float32), (width, torch.int32), (height, torch.int32)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
+                    not t.is_contiguous():
+                raise ValueError("polish: inputs must be contiguous CUDA tensors of the C types")
+        n = results.shape[0]
+        if results.dim() != 2 or results.shape[1] != RESULT_DTYPE.itemsize or hyps.dim() != 3 or \
+                hyps.shape[0] != n or hyps.shape[2] != HYP_DTYPE.itemsize or \
+                key_left.shape != key_right.shape or key_left.dim() != 3 or \
+                key_left.shape[0] != n or key_left.shape[2] != 2 or width.numel() != n or \
+                height.numel() != n:
+            raise ValueError("polish: results [P, 64], hyps [P, iters, 120], keys [P, stride, 2], "
+                             "width / height [P] expected")
+        dev = results.device
+        rounds = int(rounds)
+        inp = PolishInputs(n, hyps.shape[1], key_left.shape[1], key_left.data_ptr(),
+                           key_right.data_ptr(), width.data_ptr(), height.data_ptr(),
+                           results.data_ptr(), hyps.data_ptr())
+        out = {"polish": torch.empty((n, POLISH_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
+        if want_rounds:
+            out["rounds"] = torch.empty((n, max(rounds, 0), POLISH_ROUND_DTYPE.itemsize),
+                                        dtype=torch.uint8, device=dev)
+        if want_mask:
+            out["mask"] = torch.empty((n, key_left.shape[1]), dtype=torch.uint8, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self.L.erp_polish_dev(self.h, C.byref(inp), valid_abs, thr, rounds,
+                                    out["polish"].data_ptr(),
+                                    out["rounds"].data_ptr() if want_rounds and rounds > 0 else None,
+                                    out["mask"].data_ptr() if want_mask else None, st),
+              "erp_polish_dev")
+        return out
 
     def stage_times(self) -> dict:
         """{stage: (total_ms, launches)} since the last call (syncs on the recorded events)."""

@@ -44,6 +44,9 @@ enum CtxSlot {
     // sweep.hip: the group's rotated images, the left image's keypoints / descriptors / counts,
     // the matched keypoints of erp_image_sweep_run's match error
     kSlotSweepCanvas, kSlotLeftKp, kSlotLeftDesc, kSlotLeftCount, kSlotSweepKeyL, kSlotSweepKeyR,
+    // polish.hip: the device side of erp_eight_point_find_polished (hypothesis records, polish
+    // record, W / H, mask)
+    kSlotPolishHost,
     kCtxSlotCount
 };
 

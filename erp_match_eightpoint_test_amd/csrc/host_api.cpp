@@ -79,6 +79,27 @@ void eight_point::find(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyP
           "find");
 }
 
+void eight_point::find_polished(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
+                                Vec3f& R, Vec3f& T, int match_size, float thr, int rounds,
+                                std::vector<uint8_t>* inlier_mask) {
+    if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
+        throw error(ERP_INVALID_ARG, "find_polished: match_size");
+    std::vector<erp_point2f> a((size_t)match_size), b((size_t)match_size);
+    for (int i = 0; i < match_size; i++) {
+        a[i] = erp_point2f{kl[i].pt.x, kl[i].pt.y};
+        b[i] = erp_point2f{kr[i].pt.x, kr[i].pt.y};
+    }
+    if (inlier_mask) inlier_mask->assign((size_t)match_size, 0);
+    check(erp_eight_point_find_polished(ctx_, W, H, a.data(), b.data(), match_size, &cfg, thr,
+                                        rounds, &last_, &last_polish_,
+                                        inlier_mask && match_size > 0 ? inlier_mask->data() : nullptr),
+          "find_polished");
+    for (int k = 0; k < 3; k++) {
+        R[k] = last_polish_.R[k];
+        T[k] = last_polish_.T[k];
+    }
+}
+
 void eight_point::initial_guess(int, int, std::vector<Point3d>& l, std::vector<Point3d>& r, Vec3f& R,
                                 Vec3f& T, int match_size) {
     if (match_size < 0 || (size_t)match_size > l.size() || (size_t)match_size > r.size())

@@ -25,6 +25,15 @@ public:
     // src/eight_point.hpp:11-14
     void find(int im_width, int im_height, std::vector<KeyPoint>& key_left,
               std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out, int match_size);
+    // find followed by the polish stage (erp_match.h "polish"; no reference counterpart): the
+    // winner's inliers under |l^T E' r| < thr and up to `rounds` (0..8) refits on them.
+    // R_vec_out / T_vec_out: the last accepted state (rounds = 0: find's answer); inlier_mask
+    // (may be nullptr) is resized to match_size, 1 = inlier of that state.  last_result() is
+    // find's record, last_polish() the polish record.  Draws from the stream as find does.
+    void find_polished(int im_width, int im_height, std::vector<KeyPoint>& key_left,
+                       std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out,
+                       int match_size, float thr, int rounds,
+                       std::vector<uint8_t>* inlier_mask = nullptr);
     // src/eight_point.hpp:15-19
     void eight_point_estimation(int im_width, int im_height, std::vector<Point3d>& key_point_left_rect,
                                 std::vector<Point3d>& key_point_right_rect, Vec3f& R1_vec,
@@ -43,10 +52,12 @@ public:
 
     erp_ransac_cfg cfg;                 // reference constants (erp_ransac_cfg_default)
     const erp_pair_result& last_result() const { return last_; }
+    const erp_polish_result& last_polish() const { return last_polish_; }
 
 private:
     erp_ctx* ctx_ = nullptr;
     erp_pair_result last_{};
+    erp_polish_result last_polish_{};
 };
 
 }  // namespace erp

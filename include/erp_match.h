@@ -431,6 +431,100 @@ erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* batch, float r
                               const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
                               void* stream);
 
+/* ---- polish: the winner's inlier set and an iterated inlier refit ----
+   No reference counterpart; an opt-in extra like erp_ransac_cfg.inlier_thr.  find returns the
+   rotation of ONE 25 % random subset (the consensus winner, src/eight_point.cpp:99-149); with
+   wrong matches in the list that answer is often degrees off.  The polish says which matches
+   are the winner's inliers and refits eight_point_estimation on them, repeated while the inlier
+   set grows.  It is a stage behind find: it reads what erp_pair_batch_run /
+   erp_eight_point_find_dev wrote and changes none of it; it draws no rand(), so it never
+   touches a rand stream.
+   Per pair, from its result record (status, M, min_idx, R, T), its `iters` hypothesis records,
+   its gathered matched keypoints key_left / key_right, W, H, a threshold thr > 0 and rounds in
+   0..8; all arithmetic fp64 unless stated:
+   1. Winner.  Rows are pushed R1 then R2 per record (src/eight_point.cpp:113-126); winner_iter
+      is the iteration whose record pushed row min_idx, winner_which 0 for R1 and 1 for R2.
+   2. Start state.  e_0 = that record's E; R_0, T_0 = the result record's R, T.
+   3. Bearings.  l_i, r_i of every match i < M from the pixels, as find computes them
+      (src/eight_point.cpp:163-186).
+   4. Inlier set.  For a solved vector e: E' = its rank-2 correction (:45-50), S(e) = the
+      matches with |l_i^T E' r_i| < thr, the residual in the fixed order given at
+      erp_ransac_cfg.inlier_thr (thr widened from float).
+   5. Rounds.  S_0 = S(e_0).  For r = 1..rounds:
+        stop if |S_{r-1}| < 9 (below 9 rows the reference's thin-SVD rule applies, and such a
+        refit returns "valid" rotations that are radians off);
+        e_r = eight_point_estimation on the matches of S_{r-1} (the 36 Gram sums in a fixed
+        order, the smallest eigenvector, the estimate with the caller's valid_abs);
+        the candidates are the valid ones of R1, R2: stop if there is none;
+        R_r = the candidate nearer to R_{r-1} by the consensus' float distance (sqrtf of the
+        float squared differences; R1 on a tie), which_r = 0 / 1 says which;
+        T_r = the estimate's T, negated if (double)T[0] T_{r-1}[0] + .. [1] + .. [2] (left to
+        right) < 0;
+        S_r = S(e_r); stop and discard the round if |S_r| < |S_{r-1}|;
+        otherwise the round is accepted; stop after it if S_r = S_{r-1} as a set (further
+        rounds would repeat it).
+   6. Outputs.  rounds_done = the accepted rounds; R, T, E = the last accepted state (with
+      rounds_done = 0 the winner's R, T and E byte for byte); n_inliers = |S_rounds_done|,
+      n_inliers_winner = |S_0|; the mask = S_rounds_done, one byte (1 / 0) per match and 0 from
+      M up to key_stride.  So |S_r| never decreases and rounds = 0 gives the winner's set.
+   7. A pair whose record status is not ERP_OK gets that status and zeros (record, rounds and
+      mask) -- not an error of the call.  An M above key_stride counts as key_stride, a negative
+      one as 0 (as erp_match_error_dev); a pair with more than 65535 matches gets
+      ERP_INVALID_ARG, one whose min_idx names no row of its records ERP_INTERNAL.
+   The outputs of a pair do not depend on the other pairs of the call and are bit-identical
+   from run to run.  The stage is not timed by erp_ctx_set_profiling. */
+typedef struct erp_polish_round {   /* one accepted round r (1-based) */
+    float R[3];
+    float T[3];
+    int32_t n_fit;       /* |S_{r-1}|: the matches the refit ran on */
+    int32_t n_inliers;   /* |S_r| */
+    int32_t which;       /* 0: R = the estimate's R1, 1: its R2 */
+    int32_t reserved;
+    double E[9];         /* e_r, the solved 9-vector (sign arbitrary) */
+} erp_polish_round;
+typedef struct erp_polish_result {
+    float R[3];
+    float T[3];
+    int32_t status;      /* the pair's erp_status */
+    int32_t winner_iter;
+    int32_t winner_which;
+    int32_t rounds_done;
+    int32_t n_inliers;
+    int32_t n_inliers_winner;
+    double E[9];
+} erp_polish_result;
+/* device pointers: what a run with out->results, hyps, key_left, key_right wrote (key_stride =
+   its max_nq), or one erp_eight_point_find_dev (n_pairs 1, key_stride >= m) */
+typedef struct erp_polish_inputs {
+    int32_t n_pairs;
+    int32_t iters;                  /* records per pair (cfg->iters of the producing call) */
+    int64_t key_stride;             /* keypoint slots per pair */
+    const erp_point2f* key_left;    /* [n_pairs][key_stride] */
+    const erp_point2f* key_right;   /* [n_pairs][key_stride] */
+    const int32_t* width;           /* [n_pairs] */
+    const int32_t* height;          /* [n_pairs] */
+    const erp_pair_result* results; /* [n_pairs] */
+    const erp_hypothesis* hyps;     /* [n_pairs][iters] */
+} erp_polish_inputs;
+/* device pointers, asynchronous on `stream`, no device-to-host copy and no synchronisation:
+   one launch, one workgroup per pair, every round inside it.  valid_abs: the producing call's
+   cfg->valid_abs.  d_out [n_pairs]; d_rounds [n_pairs][rounds] (may be NULL; records past
+   rounds_done are zero); d_mask [n_pairs][key_stride] (may be NULL).  n_pairs == 0: ERP_OK,
+   nothing is done.  thr <= 0, rounds outside 0..8, iters < 1 or key_stride < 0:
+   ERP_INVALID_ARG before any GPU work.  The call allocates nothing. */
+erp_status erp_polish_dev(erp_ctx* ctx, const erp_polish_inputs* in, double valid_abs, float thr,
+                          int32_t rounds, erp_polish_result* d_out, erp_polish_round* d_rounds,
+                          uint8_t* d_mask, void* stream);
+/* host pointers, synchronous: erp_eight_point_find with the hypothesis records kept on the
+   device, followed by the polish.  A consuming call on a rand stream exactly as
+   erp_eight_point_find is.  h_result, h_polish and h_mask [m] may be NULL.  Returns the find's
+   status (h_polish->status repeats it). */
+erp_status erp_eight_point_find_polished(erp_ctx* ctx, int32_t W, int32_t H,
+                                         const erp_point2f* h_kl, const erp_point2f* h_kr,
+                                         int32_t m, const erp_ransac_cfg* cfg, float thr,
+                                         int32_t rounds, erp_pair_result* h_result,
+                                         erp_polish_result* h_polish, uint8_t* h_mask);
+
 /* ---- ERP remaps around the hot path ----
    Images are 8-bit 3-channel (CV_8UC3, BGR) H x W x 3, row-major, device pointers.  Output
    pixels whose inverse-warped source falls outside the image are NOT written (the reference
