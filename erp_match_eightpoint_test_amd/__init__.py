@@ -26,14 +26,15 @@ import ctypes as C
 import numpy as np
 
 from . import capi, synth
-from .capi import (DMATCH_DTYPE, HYP_DTYPE, POLISH_DTYPE, POLISH_ROUND_DTYPE, RESULT_DTYPE, Context,
-                   ErpError, RandStream, check, default_cfg, process_rand_stream)
+from .capi import (DMATCH_DTYPE, HYP_DTYPE, POLISH_DTYPE, POLISH_ROUND_DTYPE, RESULT_DTYPE,
+                   WINNER_DTYPE, Context, ErpError, RandStream, check, default_cfg,
+                   process_rand_stream)
 
 __all__ = ["feature_matcher", "eight_point", "erp_rotation", "spherical_surf", "epipolar_tool",
            "PairBatchRunner", "Context", "ErpError", "RandStream", "process_rand_stream",
            "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "POLISH_DTYPE",
-           "POLISH_ROUND_DTYPE", "results_to_numpy", "hyps_to_numpy", "polish_to_numpy",
-           "polish_rounds_to_numpy", "sweep_relative_rotation", "synth", "capi"]
+           "POLISH_ROUND_DTYPE", "WINNER_DTYPE", "results_to_numpy", "hyps_to_numpy",
+           "polish_to_numpy", "polish_rounds_to_numpy", "winners_to_numpy", "sweep_relative_rotation", "synth", "capi"]
 
 
 def _np_ptr(a: np.ndarray):
@@ -175,6 +176,7 @@ class eight_point:  # noqa: N801  (reference class name)
         self.cfg = default_cfg(**cfg)
         self.last_result = None
         self.last_polish = None
+        self.last_winner = None
         if stream is not None:
             self.ctx.set_rand_stream(stream)
 
@@ -197,6 +199,31 @@ class eight_point:  # noqa: N801  (reference class name)
         self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
         check(st, "find")
         return R, T
+
+    def find_winner(self, im_width: int, im_height: int, key_left, key_right,
+                    match_size: int | None = None):
+        """find plus the winning iteration's essential matrix (erp_eight_point_find_winner; no
+        reference counterpart) -> (R (3,), T (3,), E (3, 3) float64): E is the solved 9-vector
+        R and T were decomposed from (sign arbitrary), e.g. for epipolar_tool.draw_epipole.
+        ``last_winner`` is the record (WINNER_DTYPE: status, iter, which, sample_n, E)."""
+        kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
+        kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
+        m = kl.shape[0] if match_size is None else int(match_size)
+        if m > kl.shape[0] or m > kr.shape[0]:
+            raise ValueError("match_size larger than the keypoint arrays")
+        kl = np.ascontiguousarray(kl[:m])
+        kr = np.ascontiguousarray(kr[:m])
+        R = np.zeros(3, np.float32)
+        T = np.zeros(3, np.float32)
+        res, win = capi.PairResult(), capi.Winner()
+        st = self.ctx.L.erp_eight_point_find_winner(self.ctx.h, im_width, im_height, _np_ptr(kl),
+                                                    _np_ptr(kr), m, C.byref(self.cfg), _np_ptr(R),
+                                                    _np_ptr(T), C.byref(res), C.byref(win))
+        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
+        self.last_winner = np.frombuffer(bytes(win), WINNER_DTYPE)[0]
+        check(st, "find_winner")
+        check(int(self.last_winner["status"]), "find_winner: winner record")
+        return R, T, self.last_winner["E"].reshape(3, 3).copy()
 
     def find_polished(self, im_width: int, im_height: int, key_left, key_right, thr: float,
                       rounds: int = 3, match_size: int | None = None):
@@ -860,7 +887,8 @@ class PairBatchRunner:
     run(...) launches match -> gather -> find for every pair on torch's current stream and
     returns a torch uint8 tensor of erp_pair_result records (view with RESULT_DTYPE after
     .cpu()).  Optional debug outputs (matches, hyps, samples, rvec, tvec, dist) are allocated
-    when requested.
+    when requested; want=("winners",) adds the winner records (uint8 [P, 88], WINNER_DTYPE: the
+    winning iteration's E without the hypothesis records) through erp_pair_batch_run_winners.
     """
 
     def __init__(self, device: int = 0, ctx: Context | None = None, reuse_outputs: bool = False,
@@ -911,7 +939,8 @@ class PairBatchRunner:
                   "samples": (n_pairs, iters, s_max, torch.int32),
                   "rvec": (n_pairs, 2 * iters, 3, torch.float32),
                   "tvec": (n_pairs, 2 * iters, 3, torch.float32),
-                  "dist": (n_pairs, 2 * iters, torch.float64)}
+                  "dist": (n_pairs, 2 * iters, torch.float64),
+                  "winners": (n_pairs, WINNER_DTYPE.itemsize, torch.uint8)}
         for name in want:
             *shape, dt = shapes[name]
             outs[name] = torch.zeros(shape, dtype=dt, device=dev)
@@ -1024,18 +1053,24 @@ class PairBatchRunner:
     def polish(self, out: dict, width, height, thr: float, rounds: int = 3,
                want_rounds: bool = False, stream=None) -> dict:
         """The polish stage (include/erp_match.h "polish"; no reference counterpart) on the dict
-        ``run(..., want=("hyps", "key_left", "key_right"))`` returned: the inlier set of every
+        ``run(..., want=("hyps", "key_left", "key_right"))`` returned -- or, without the
+        hypothesis records, ``want=("winners", "key_left", "key_right")`` (the lite route;
+        ``hyps`` is used when both are there): the inlier set of every
         pair's winner under |l^T E' r| < thr and up to ``rounds`` refits on it -> {"polish":
         records (polish_to_numpy), "mask": uint8 [P, max_nq] (1 = inlier of the final state),
         "rounds": the per-round records (want_rounds; polish_rounds_to_numpy)}.  One launch on
         torch's current stream (or ``stream``), nothing leaves the device; ``out`` is only read."""
-        missing = [k for k in ("results", "hyps", "key_left", "key_right") if k not in out]
+        missing = [k for k in ("results", "key_left", "key_right") if k not in out]
+        if "hyps" not in out and "winners" not in out:
+            missing.append("hyps")
         if missing:
-            raise ValueError(f"polish needs run(..., want=('hyps', 'key_left', 'key_right')): "
-                             f"missing {missing}")
-        return self.ctx.polish(out["results"], out["hyps"], out["key_left"], out["key_right"],
-                               width, height, thr, rounds=rounds, valid_abs=self.cfg.valid_abs,
-                               want_rounds=want_rounds, stream=stream)
+            raise ValueError(f"polish needs run(..., want=('hyps', 'key_left', 'key_right')) or "
+                             f"want=('winners', 'key_left', 'key_right'): missing {missing}")
+        use_hyps = "hyps" in out
+        return self.ctx.polish(out["results"], out["hyps"] if use_hyps else None, out["key_left"],
+                               out["key_right"], width, height, thr, rounds=rounds,
+                               valid_abs=self.cfg.valid_abs, want_rounds=want_rounds,
+                               stream=stream, winners=None if use_hyps else out["winners"])
 
     def _launch(self, b, ratio, outs, stream, dev):
         import torch
@@ -1043,6 +1078,12 @@ class PairBatchRunner:
                                 for k in ("results", "matches", "key_left", "key_right", "hyps",
                                           "samples", "rvec", "tvec", "dist")])
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        if "winners" in outs:
+            check(self.ctx.L.erp_pair_batch_run_winners(self.ctx.h, C.byref(b), ratio,
+                                                        C.byref(self.cfg), C.byref(o),
+                                                        outs["winners"].data_ptr(), st),
+                  "erp_pair_batch_run_winners")
+            return outs
         check(self.ctx.L.erp_pair_batch_run(self.ctx.h, C.byref(b), ratio, C.byref(self.cfg),
                                             C.byref(o), st), "erp_pair_batch_run")
         return outs
@@ -1055,6 +1096,11 @@ def results_to_numpy(t) -> np.ndarray:
 def polish_to_numpy(t) -> np.ndarray:
     """erp_polish_result records (Context.polish / PairBatchRunner.polish "polish") -> [P]"""
     return t.cpu().numpy().view(POLISH_DTYPE).reshape(-1)
+
+
+def winners_to_numpy(t) -> np.ndarray:
+    """erp_winner records (run(..., want=("winners",)) "winners") -> [P]"""
+    return t.cpu().numpy().view(WINNER_DTYPE).reshape(-1)
 
 
 def polish_rounds_to_numpy(t) -> np.ndarray:

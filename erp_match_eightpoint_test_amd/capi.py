@@ -86,6 +86,11 @@ class PolishInputs(C.Structure):
                 ("hyps", P)]
 
 
+class Winner(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iter", C.c_int32), ("which", C.c_int32),
+                ("sample_n", C.c_int32), ("E", C.c_double * 9)]
+
+
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"),
                          ("distance", "<f4")])
 HYP_DTYPE = np.dtype([("R1", "<f4", 3), ("R2", "<f4", 3), ("T", "<f4", 3), ("R1_valid", "<i4"),
@@ -101,7 +106,10 @@ POLISH_DTYPE = np.dtype([("R", "<f4", 3), ("T", "<f4", 3), ("status", "<i4"),
                          ("winner_iter", "<i4"), ("winner_which", "<i4"), ("rounds_done", "<i4"),
                          ("n_inliers", "<i4"), ("n_inliers_winner", "<i4"), ("E", "<f8", 9)],
                         align=True)
+WINNER_DTYPE = np.dtype([("status", "<i4"), ("iter", "<i4"), ("which", "<i4"), ("sample_n", "<i4"),
+                         ("E", "<f8", 9)], align=True)
 POLISH_MAX_ROUNDS = 8
+assert WINNER_DTYPE.itemsize == C.sizeof(Winner) == 88
 assert DMATCH_DTYPE.itemsize == C.sizeof(DMatch) == 16
 assert POLISH_ROUND_DTYPE.itemsize == C.sizeof(PolishRound) == 112
 assert POLISH_DTYPE.itemsize == C.sizeof(PolishResult) == 120
@@ -133,7 +141,9 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_rand_stream_shuffle_prefix", "erp_image_sweep_features_dev",
             "erp_image_sweep_run", "erp_match_error_dev", "erp_vertical_rotate_batch_dev",
             "erp_rectify_batch_dev", "erp_rectify_results_dev", "erp_rectify_matrices_results",
-            "erp_polish_dev", "erp_eight_point_find_polished"]
+            "erp_polish_dev", "erp_eight_point_find_polished", "erp_pair_batch_run_winners",
+            "erp_eight_point_find_winner_dev", "erp_eight_point_find_winner",
+            "erp_polish_winners_dev"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -308,6 +318,14 @@ def load(build_if_missing: bool = False):
     L.erp_eight_point_find_polished.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
                                                 C.POINTER(RansacCfg), C.c_float, C.c_int32, P, P,
                                                 P]
+    L.erp_pair_batch_run_winners.argtypes = [P, C.POINTER(PairBatch), C.c_float,
+                                             C.POINTER(RansacCfg), C.POINTER(BatchOutputs), P, P]
+    L.erp_eight_point_find_winner_dev.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
+                                                  C.POINTER(RansacCfg), P, P, P, P]
+    L.erp_eight_point_find_winner.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
+                                              C.POINTER(RansacCfg), P, P, P, P]
+    L.erp_polish_winners_dev.argtypes = [P, C.POINTER(PolishInputs), P, C.c_double, C.c_float,
+                                         C.c_int32, P, P, P, P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]
@@ -427,31 +445,38 @@ class Context:
 
     def polish(self, results, hyps, key_left, key_right, width, height, thr: float,
                rounds: int = 3, valid_abs: float = 1.57, want_rounds: bool = False,
-               want_mask: bool = True, stream=None) -> dict:
+               want_mask: bool = True, stream=None, winners=None) -> dict:
         """erp_polish_dev on torch CUDA tensors: results [P, 64] uint8, hyps [P, iters, 120]
         uint8, key_left / key_right [P, stride, 2] float32, width / height [P] int32 -> {"polish":
         uint8 [P, 120] (POLISH_DTYPE), "rounds": uint8 [P, rounds, 112] (want_rounds), "mask":
         uint8 [P, stride] (want_mask)}.  Asynchronous on ``stream`` (default: torch's current
-        stream); valid_abs = the cfg.valid_abs of the call that wrote the records."""
+        stream); valid_abs = the cfg.valid_abs of the call that wrote the records.
+        ``hyps=None, winners=`` uint8 [P, 88] (WINNER_DTYPE, what erp_pair_batch_run_winners
+        wrote): erp_polish_winners_dev, the same outputs without the hypothesis records."""
         import torch
-        for t, dt in ((results, torch.uint8), (hyps, torch.uint8), (key_left, torch.float32),
+        from_winners = hyps is None
+        rec = winners if from_winners else hyps
+        for t, dt in ((results, torch.uint8), (rec, torch.uint8), (key_left, torch.float32),
                       (key_right, torch.float32), (width, torch.int32), (height, torch.int32)):
             if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
                     not t.is_contiguous():
                 raise ValueError("polish: inputs must be contiguous CUDA tensors of the C types")
         n = results.shape[0]
-        if results.dim() != 2 or results.shape[1] != RESULT_DTYPE.itemsize or hyps.dim() != 3 or \
-                hyps.shape[0] != n or hyps.shape[2] != HYP_DTYPE.itemsize or \
+        rec_ok = (rec.dim() == 2 and rec.shape[1] == WINNER_DTYPE.itemsize) if from_winners else \
+            (rec.dim() == 3 and rec.shape[2] == HYP_DTYPE.itemsize)
+        if results.dim() != 2 or results.shape[1] != RESULT_DTYPE.itemsize or not rec_ok or \
+                rec.shape[0] != n or \
                 key_left.shape != key_right.shape or key_left.dim() != 3 or \
                 key_left.shape[0] != n or key_left.shape[2] != 2 or width.numel() != n or \
                 height.numel() != n:
-            raise ValueError("polish: results [P, 64], hyps [P, iters, 120], keys [P, stride, 2], "
-                             "width / height [P] expected")
+            raise ValueError("polish: results [P, 64], hyps [P, iters, 120] (or winners [P, 88]), "
+                             "keys [P, stride, 2], width / height [P] expected")
         dev = results.device
         rounds = int(rounds)
-        inp = PolishInputs(n, hyps.shape[1], key_left.shape[1], key_left.data_ptr(),
-                           key_right.data_ptr(), width.data_ptr(), height.data_ptr(),
-                           results.data_ptr(), hyps.data_ptr())
+        inp = PolishInputs(n, 0 if from_winners else hyps.shape[1], key_left.shape[1],
+                           key_left.data_ptr(), key_right.data_ptr(), width.data_ptr(),
+                           height.data_ptr(), results.data_ptr(),
+                           None if from_winners else hyps.data_ptr())
         out = {"polish": torch.empty((n, POLISH_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
         if want_rounds:
             out["rounds"] = torch.empty((n, max(rounds, 0), POLISH_ROUND_DTYPE.itemsize),
@@ -459,11 +484,14 @@ class Context:
         if want_mask:
             out["mask"] = torch.empty((n, key_left.shape[1]), dtype=torch.uint8, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self.L.erp_polish_dev(self.h, C.byref(inp), valid_abs, thr, rounds,
-                                    out["polish"].data_ptr(),
-                                    out["rounds"].data_ptr() if want_rounds and rounds > 0 else None,
-                                    out["mask"].data_ptr() if want_mask else None, st),
-              "erp_polish_dev")
+        tail = (valid_abs, thr, rounds, out["polish"].data_ptr(),
+                out["rounds"].data_ptr() if want_rounds and rounds > 0 else None,
+                out["mask"].data_ptr() if want_mask else None, st)
+        if from_winners:
+            check(self.L.erp_polish_winners_dev(self.h, C.byref(inp), winners.data_ptr(), *tail),
+                  "erp_polish_winners_dev")
+        else:
+            check(self.L.erp_polish_dev(self.h, C.byref(inp), *tail), "erp_polish_dev")
         return out
 
     def stage_times(self) -> dict:

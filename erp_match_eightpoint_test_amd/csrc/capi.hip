@@ -387,6 +387,12 @@ erp_status run_inliers(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_c
 bool use_lite(const erp_ransac_cfg* cfg, const erp_batch_outputs* out) {
     return !(out && out->hyps) && !(cfg->inlier_thr > 0.0f) && ERP_FUSE_EIGEN != 2;
 }
+// whether a launch shares replays (run_hypotheses below says why and when): the pairs' selection
+// words then belong to pair rep[p] (c->rep)
+bool share_replays(const erp_ctx* c, const erp::BatchShape& sh, bool on_stream) {
+    return c->opt[ERP_OPT_SAMPLER_SHARE] != 0 && !on_stream && sh.n_pairs >= 2 &&
+           sh.n_pairs <= erp::kAliasMaxPairs;
+}
 // estimator stages after counts/pts are in place (lite: the estimates in the lite layout)
 erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ransac_cfg* cfg,
                           const erp_batch_outputs* out, hipStream_t st, bool lite = false,
@@ -408,8 +414,7 @@ erp_status run_hypotheses(erp_ctx* c, const erp::BatchShape& sh_in, const erp_ra
     // stream (every pair has its own window), not for one pair, not above the table's pair
     // limit.  Built on the stream from the device's counts (no sync), whatever stage groups the
     // debug mask leaves on: the table is as cheap as deciding who needs it.
-    if (c->opt[ERP_OPT_SAMPLER_SHARE] != 0 && !on_stream && sh.n_pairs >= 2 &&
-        sh.n_pairs <= erp::kAliasMaxPairs) {
+    if (share_replays(c, sh, on_stream)) {
         StageTimer _t(ctx, ERP_STAGE_JUMP_PREP, st);
         ERP_CK(erp::launch_sampler_alias(counts, sh, cfg->sample_frac, (int32_t*)c->rep.p, st));
         sh.rep = (const int32_t*)c->rep.p;
@@ -625,6 +630,40 @@ erp_status run_estimator(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac
     return run_consensus(c, sh, cfg, out, results, st, true, cc);
 }
 
+// The winner stage behind run_estimator (winner.hip; include/erp_match.h "winner records"): one
+// launch over what the run left in the scratch.  Nothing between the estimate and the end of
+// run_consensus writes what it reads: the consensus takes counts, flags and hlite (hl, wsum) as
+// inputs only (launch_valid_place reads them into rv / tv), and idx, pts and rep are not among
+// its buffers at all (ConsensusBufs).  The callers refuse a partial ERP_OPT_DEBUG_STAGES mask,
+// which would leave another call's scratch in place.
+erp_status run_winners(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_cfg* cfg,
+                       const erp_batch_outputs* out, const erp_pair_result* results,
+                       erp_winner* winners, hipStream_t st) {
+    const bool lite = use_lite(cfg, out);
+    const erp::ConsensusLayout L = erp::consensus_layout(sh.n_pairs, sh.iters);
+    erp::WinnerArgs a{};
+    a.results = results;
+    if (lite) {
+        a.hl = erp::ws_at<float>(c->hlite.p, L.hlite.hl);
+        a.wsum = erp::ws_at<int32_t>(c->hlite.p, L.hlite.wsum);
+    } else {
+        a.hyps = (out && out->hyps) ? out->hyps : (const erp_hypothesis*)c->hyps.p;
+    }
+    a.counts = (const int32_t*)c->counts.p;
+    a.pts = (const double*)c->pts.p;
+    a.selw = (const uint32_t*)c->idx.p;
+    a.rep = share_replays(c, sh, c->rs != nullptr) ? (const int32_t*)c->rep.p : nullptr;
+    a.iters = sh.iters;
+    a.nwaves = (sh.iters + 63) / 64;
+    a.nbw = sh.sel_words;
+    a.max_nq = sh.max_nq;
+    a.sample_frac = cfg->sample_frac;
+    a.valid_abs = cfg->valid_abs;
+    a.out = winners;
+    ERP_CK(erp::launch_winner(a, sh.n_pairs, st));
+    return ERP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -788,9 +827,11 @@ erp_status erp_ctx_get_option(erp_ctx* ctx, int32_t option, int32_t* value) {
 
 void erp_debug_set_alloc_pad(size_t bytes) { g_alloc_pad.store(bytes, std::memory_order_relaxed); }
 
-erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio,
-                              const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
-                              void* stream) {
+// erp_pair_batch_run (winners == nullptr) and erp_pair_batch_run_winners, which appends the
+// winner stage and always enqueues plainly
+static erp_status pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio,
+                                 const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
+                                 erp_winner* winners, void* stream) {
     if (!ctx || !b || !out || !out->results || !cfg_ok(cfg)) return ERP_INVALID_ARG;
     if (b->n_pairs < 1 || b->dim != erp::kDim || b->max_nq < 0 || b->max_nt < 0 ||
         b->max_nq > 65535 || !b->desc_l || !b->desc_r || !b->kp_l || !b->kp_r || !b->off_l ||
@@ -799,6 +840,7 @@ erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     CtxCall call(ctx, st);
+    if (winners && ctx->opt[ERP_OPT_DEBUG_STAGES] != -1) return ERP_INVALID_ARG;
     const erp::BatchShape sh = make_shape(b->n_pairs, b->max_nq, b->max_nt, cfg->iters,
                                           cfg->sample_frac);
     if (!ensure_matcher(ctx, sh)) return ERP_OUT_OF_MEMORY;
@@ -820,12 +862,13 @@ erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (st != nullptr) ERP_CK(hipStreamIsCapturing(st, &cap));
     if (!ctx->use_graphs || ctx->profiling || st == nullptr || ctx->opt[ERP_OPT_DEBUG_SNAP] ||
-        cap != hipStreamCaptureStatusNone) {
+        cap != hipStreamCaptureStatusNone || winners) {
         // (inside the caller's own capture the stream's event cannot order anything: the
         // caller's graph then owns the order of the calls that share the stream)
         ctx->rs_capture = cap != hipStreamCaptureStatusNone;
         es = batch_enqueue(ctx, b, ratio, cfg, out, sh, matches, st);
         ctx->rs_capture = false;
+        if (es == ERP_OK && winners) es = run_winners(ctx, sh, cfg, out, out->results, winners, st);
         return es;
     }
     // graph replay: the same call (structs, buffers, scratch) as a captured one -> one launch.
@@ -868,6 +911,19 @@ erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio
     }
     ctx->graphs.push_back({std::move(key), exec, ++ctx->graph_clock});
     return launch(exec);
+}
+
+erp_status erp_pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio,
+                              const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
+                              void* stream) {
+    return pair_batch_run(ctx, b, ratio, cfg, out, nullptr, stream);
+}
+
+erp_status erp_pair_batch_run_winners(erp_ctx* ctx, const erp_pair_batch* b, float ratio,
+                                      const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
+                                      erp_winner* d_winners, void* stream) {
+    if (!d_winners) return ERP_INVALID_ARG;
+    return pair_batch_run(ctx, b, ratio, cfg, out, d_winners, stream);
 }
 
 erp_status erp_match_knn2_ratio(erp_ctx* ctx, const float* d_query, int32_t nq,
@@ -920,10 +976,11 @@ erp_status erp_match_two_image(erp_ctx* ctx, const float* h_desc1, int32_t n1, c
     return ERP_OK;
 }
 
-erp_status erp_eight_point_find_dev(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* d_kl,
-                                    const erp_point2f* d_kr, int32_t m, const erp_ransac_cfg* cfg,
-                                    erp_pair_result* d_result, erp_hypothesis* d_hyps,
-                                    void* stream) {
+// erp_eight_point_find_dev (d_winner == nullptr) and erp_eight_point_find_winner_dev
+static erp_status find_dev(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* d_kl,
+                           const erp_point2f* d_kr, int32_t m, const erp_ransac_cfg* cfg,
+                           erp_pair_result* d_result, erp_hypothesis* d_hyps,
+                           erp_winner* d_winner, void* stream) {
     if (!ctx || W <= 0 || H <= 0 || m < 0 || m > 65535 || !d_result || !cfg_ok(cfg) ||
         !sampler_m_ok(cfg, m))
         return ERP_INVALID_ARG;
@@ -931,6 +988,7 @@ erp_status erp_eight_point_find_dev(erp_ctx* ctx, int32_t W, int32_t H, const er
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     CtxCall call(ctx, st);
+    if (d_winner && ctx->opt[ERP_OPT_DEBUG_STAGES] != -1) return ERP_INVALID_ARG;
     const erp::BatchShape sh = make_shape(1, m, m, cfg->iters, cfg->sample_frac);
     erp_batch_outputs out{};
     out.results = d_result;
@@ -945,7 +1003,25 @@ erp_status erp_eight_point_find_dev(erp_ctx* ctx, int32_t W, int32_t H, const er
         StageTimer _t(ctx, ERP_STAGE_BEARINGS, st);
         ERP_CK(erp::launch_bearings_direct(d_kl, d_kr, m, W, H, (double*)ctx->pts.p, st));
     }
-    return run_estimator(ctx, sh, cfg, &out, d_result, st);
+    es = run_estimator(ctx, sh, cfg, &out, d_result, st);
+    if (es == ERP_OK && d_winner) es = run_winners(ctx, sh, cfg, &out, d_result, d_winner, st);
+    return es;
+}
+
+erp_status erp_eight_point_find_dev(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* d_kl,
+                                    const erp_point2f* d_kr, int32_t m, const erp_ransac_cfg* cfg,
+                                    erp_pair_result* d_result, erp_hypothesis* d_hyps,
+                                    void* stream) {
+    return find_dev(ctx, W, H, d_kl, d_kr, m, cfg, d_result, d_hyps, nullptr, stream);
+}
+
+erp_status erp_eight_point_find_winner_dev(erp_ctx* ctx, int32_t W, int32_t H,
+                                           const erp_point2f* d_kl, const erp_point2f* d_kr,
+                                           int32_t m, const erp_ransac_cfg* cfg,
+                                           erp_pair_result* d_result, erp_hypothesis* d_hyps,
+                                           erp_winner* d_winner, void* stream) {
+    if (!d_winner) return ERP_INVALID_ARG;
+    return find_dev(ctx, W, H, d_kl, d_kr, m, cfg, d_result, d_hyps, d_winner, stream);
 }
 
 erp_status erp_eight_point_hypotheses_dev(erp_ctx* ctx, int32_t W, int32_t H,
@@ -1065,32 +1141,52 @@ erp_status erp_consensus_hyps_finish_dev(erp_ctx* ctx, int32_t m, const erp_hypo
     return consensus_hyps_call(ctx, m, d_hyps, n_hyps, cfg, cc, d_result, stream);
 }
 
-erp_status erp_eight_point_find(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* h_kl,
-                                const erp_point2f* h_kr, int32_t m, const erp_ransac_cfg* cfg,
-                                float R_out[3], float T_out[3], erp_pair_result* h_result) {
+// erp_eight_point_find (h_winner == nullptr) and erp_eight_point_find_winner: the winner record
+// sits behind the result record in the staging buffer
+static erp_status find_host(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* h_kl,
+                            const erp_point2f* h_kr, int32_t m, const erp_ransac_cfg* cfg,
+                            float R_out[3], float T_out[3], erp_pair_result* h_result,
+                            erp_winner* h_winner) {
     if (!ctx || m < 0 || (m > 0 && (!h_kl || !h_kr))) return ERP_INVALID_ARG;
     // one lock across upload, find and download: the staging buffers are the context's
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     ERP_CK(hipSetDevice(ctx->device));
     if (!ensure(ctx->in_a, (size_t)m * 8 + 8) || !ensure(ctx->in_b, (size_t)m * 8 + 8) ||
-        !ensure(ctx->in_c, sizeof(erp_pair_result)))
+        !ensure(ctx->in_c, sizeof(erp_pair_result) + sizeof(erp_winner)))
         return ERP_OUT_OF_MEMORY;
     if (m > 0) {
         ERP_CK(hipMemcpy(ctx->in_a.p, h_kl, (size_t)m * 8, hipMemcpyHostToDevice));
         ERP_CK(hipMemcpy(ctx->in_b.p, h_kr, (size_t)m * 8, hipMemcpyHostToDevice));
     }
-    erp_status s = erp_eight_point_find_dev(ctx, W, H, (const erp_point2f*)ctx->in_a.p,
-                                            (const erp_point2f*)ctx->in_b.p, m, cfg,
-                                            (erp_pair_result*)ctx->in_c.p, nullptr, nullptr);
+    erp_winner* d_winner = h_winner ? (erp_winner*)((erp_pair_result*)ctx->in_c.p + 1) : nullptr;
+    erp_status s = find_dev(ctx, W, H, (const erp_point2f*)ctx->in_a.p,
+                            (const erp_point2f*)ctx->in_b.p, m, cfg,
+                            (erp_pair_result*)ctx->in_c.p, nullptr, d_winner, nullptr);
     if (s != ERP_OK) return s;
     erp_pair_result r;
     ERP_CK(hipMemcpy(&r, ctx->in_c.p, sizeof(r), hipMemcpyDeviceToHost));
+    if (h_winner) ERP_CK(hipMemcpy(h_winner, d_winner, sizeof(*h_winner), hipMemcpyDeviceToHost));
     if (h_result) *h_result = r;
     if (R_out)
         for (int k = 0; k < 3; k++) R_out[k] = r.R[k];
     if (T_out)
         for (int k = 0; k < 3; k++) T_out[k] = r.T[k];
     return (erp_status)r.status;
+}
+
+erp_status erp_eight_point_find(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* h_kl,
+                                const erp_point2f* h_kr, int32_t m, const erp_ransac_cfg* cfg,
+                                float R_out[3], float T_out[3], erp_pair_result* h_result) {
+    return find_host(ctx, W, H, h_kl, h_kr, m, cfg, R_out, T_out, h_result, nullptr);
+}
+
+erp_status erp_eight_point_find_winner(erp_ctx* ctx, int32_t W, int32_t H,
+                                       const erp_point2f* h_kl, const erp_point2f* h_kr,
+                                       int32_t m, const erp_ransac_cfg* cfg, float R_out[3],
+                                       float T_out[3], erp_pair_result* h_result,
+                                       erp_winner* h_winner) {
+    if (!h_winner || !cfg_ok(cfg)) return ERP_INVALID_ARG;
+    return find_host(ctx, W, H, h_kl, h_kr, m, cfg, R_out, T_out, h_result, h_winner);
 }
 
 erp_status erp_initial_guess(erp_ctx* ctx, const double* h_bl, const double* h_br, int32_t m,

@@ -198,6 +198,25 @@ hipError_t launch_valid_compact(const int32_t* counts, const erp_hypothesis* hyp
                                 const BatchShape& sh, double sample_frac, int32_t* vchunk,
                                 float* rv, float* tv, int32_t* kcount, float* rv_aos,
                                 float* dscale, hipStream_t st);
+// The winner stage (winner.hip; include/erp_match.h "winner records"), after the consensus: per
+// pair the iteration that pushed row min_idx -- from the records' flags (hyps != NULL) or from
+// the lite estimates' NaN marks and per-wave counts (hl, wsum: ConsensusLayout::hlite) -- its
+// Gram re-summed from the selection words selw (pair rep[p]'s when rep != NULL) over pts, the
+// pipeline's solve, and the self-check against results[p].  Reads only; one launch.
+struct WinnerArgs {
+    const erp_pair_result* results;   // [P]
+    const erp_hypothesis* hyps;       // [P][iters], or null: the lite route
+    const float* hl;                  // [P][9][iters] (lite)
+    const int32_t* wsum;              // [P][nwaves][8] (lite)
+    const int32_t* counts;            // [P] M
+    const double* pts;                // [P][max_nq + 1][6]
+    const uint32_t* selw;             // [P][nwaves][nbw][64]
+    const int32_t* rep;               // [P] or null
+    int iters, nwaves, nbw, max_nq;
+    double sample_frac, valid_abs;
+    erp_winner* out;                  // [P]
+};
+hipError_t launch_winner(const WinnerArgs& a, int n_pairs, hipStream_t st);
 hipError_t launch_gram_all(const double* pts, int32_t m, double* gram, hipStream_t st);
 hipError_t launch_consensus_input(const float* rvec, const float* tvec, int K, int stride, float* rv,
                                   float* tv, int32_t* kcount, float* dscale, int32_t* flags,

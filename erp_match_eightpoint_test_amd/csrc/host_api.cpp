@@ -79,6 +79,21 @@ void eight_point::find(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyP
           "find");
 }
 
+void eight_point::find_winner(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
+                              Vec3f& R, Vec3f& T, int match_size, erp_winner& winner) {
+    if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
+        throw error(ERP_INVALID_ARG, "find_winner: match_size");
+    std::vector<erp_point2f> a((size_t)match_size), b((size_t)match_size);
+    for (int i = 0; i < match_size; i++) {
+        a[i] = erp_point2f{kl[i].pt.x, kl[i].pt.y};
+        b[i] = erp_point2f{kr[i].pt.x, kr[i].pt.y};
+    }
+    check(erp_eight_point_find_winner(ctx_, W, H, a.data(), b.data(), match_size, &cfg, R.val,
+                                      T.val, &last_, &winner),
+          "find_winner");
+    check((erp_status)winner.status, "find_winner: winner record");
+}
+
 void eight_point::find_polished(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
                                 Vec3f& R, Vec3f& T, int match_size, float thr, int rounds,
                                 std::vector<uint8_t>* inlier_mask) {

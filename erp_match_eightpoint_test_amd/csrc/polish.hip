@@ -5,9 +5,10 @@
 //
 // One workgroup of 256 threads per pair runs every round inside one launch:
 //   winner    block prefix scan over the records' two validity flags -> the iteration and the
-//             rotation (R1 / R2) that pushed row min_idx.  The strided read of the 120-B records
-//             is the stage's only large traffic (<= n_pairs x iters x 120 B; it stops at the
-//             256-record chunk that holds the winner).
+//             rotation (R1 / R2) that pushed row min_idx (erp_winner.hpp).  The strided read of
+//             the 120-B records is the stage's only large traffic (<= n_pairs x iters x 120 B;
+//             it stops at the 256-record chunk that holds the winner).  erp_polish_winners_dev
+//             takes both and the start E from the pair's erp_winner record instead: no records.
 //   pass      every match's residual under E' (9 doubles broadcast through LDS): a wave takes 64
 //             consecutive matches per step, its ballot is one 64-bit word of the LDS bitmap
 //             (M <= 65535: 8 KB, two of them -- the accepted set and the candidate), the wave's
@@ -31,6 +32,7 @@
 #include "erp_ctx.hpp"
 #include "erp_device.hpp"
 #include "erp_launch.hpp"
+#include "erp_winner.hpp"
 
 using erp::CtxCall;
 
@@ -38,7 +40,7 @@ namespace {
 
 using namespace erp;
 
-constexpr int kPolishThreads = 256;
+constexpr int kPolishThreads = kWinnerThreads;  // (winner_from_records' block)
 constexpr int kPolishWaves = kPolishThreads / 64;
 constexpr int kPolishMaxM = 65535;                      // as find: the bitmap's size
 constexpr int kPolishWords = (kPolishMaxM + 63) / 64;   // 64-bit words of one bitmap
@@ -53,6 +55,7 @@ struct PolishArgs {
     erp_polish_result* out;
     erp_polish_round* rounds_out;   // may be null
     uint8_t* mask;                  // may be null
+    const erp_winner* winners;      // null: the winner comes from in.hyps (erp_polish_dev)
 };
 
 // a state of the chain: the solved e, its rank-2 corrected E', the chosen rotation and T
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
     __shared__ int wsum[kPolishWaves], wcnt[kPolishWaves], wdiff[kPolishWaves];
     __shared__ int win[2];
 
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x, tid = threadIdx.x;
     const erp_pair_result* res = a.in.results + p;
     const int32_t status = res->status;
     const int64_t stride = a.in.key_stride;
@@ -177,54 +180,37 @@ __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
         return;
     }
     const int M = (int)m64;
-    const int iters = a.in.iters;
-    const erp_hypothesis* hyps = a.in.hyps + (size_t)p * iters;
 
-    // ---- the winner: the record whose R1 / R2 was pushed as row min_idx ----
-    const int min_idx = res->min_idx;
-    if (tid == 0) win[0] = -1;
-    __syncthreads();
-    int base = 0;
-    for (int h0 = 0; h0 < iters; h0 += kPolishThreads) {
-        const int h = h0 + tid;
-        int v1 = 0, c = 0;
-        if (h < iters) {
-            v1 = hyps[h].R1_valid != 0;
-            c = v1 + (hyps[h].R2_valid != 0);
+    // ---- the winner: the record whose R1 / R2 was pushed as row min_idx, from the records'
+    // flags (erp_winner.hpp) or, for erp_polish_winners_dev, from the pair's winner record ----
+    const double* e0;
+    if (a.winners) {  // (block-uniform)
+        const erp_winner* wr = a.winners + p;
+        if (wr->status != ERP_OK) {
+            polish_skip(a, p, wr->status);
+            return;
         }
-        int x = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
+        if (tid == 0) {
+            win[0] = wr->iter;
+            win[1] = wr->which;
         }
-        if (lane == 63) wsum[wave] = x;
         __syncthreads();
-        int wbase = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kPolishWaves; w++) {
-            wbase += w < wave ? wsum[w] : 0;
-            total += wsum[w];
+        e0 = wr->E;
+    } else {
+        const erp_hypothesis* hyps = a.in.hyps + (size_t)p * a.in.iters;
+        winner_from_records(hyps, a.in.iters, res->min_idx, wsum, win);
+        if (win[0] < 0) {  // min_idx names no row of these records
+            polish_skip(a, p, ERP_INTERNAL);
+            return;
         }
-        const int first = base + wbase + x - c;  // the row this record's first rotation got
-        if (c && min_idx >= first && min_idx < first + c) {
-            win[0] = h;
-            win[1] = (v1 && min_idx == first) ? 0 : 1;
-        }
-        base += total;
-        __syncthreads();
-        if (win[0] >= 0 || base > min_idx) break;
+        e0 = hyps[win[0]].E;
     }
     const int winner = win[0], winner_which = win[1];
-    if (winner < 0) {  // min_idx names no row of these records
-        polish_skip(a, p, ERP_INTERNAL);
-        return;
-    }
 
     // ---- the start state: the winner's E, the result record's R and T ----
     if (tid == 0) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) acc.e[k] = hyps[winner].E[k];
+        for (int k = 0; k < 9; k++) acc.e[k] = e0[k];
         rank2_correct(acc.e, acc.Ec);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
@@ -337,15 +323,17 @@ __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
 
 extern "C" {
 
-erp_status erp_polish_dev(erp_ctx* ctx, const erp_polish_inputs* in, double valid_abs, float thr,
-                          int32_t rounds, erp_polish_result* d_out, erp_polish_round* d_rounds,
-                          uint8_t* d_mask, void* stream) {
+// erp_polish_dev (winners == nullptr: the winner from in->hyps) and erp_polish_winners_dev
+static erp_status polish_call(erp_ctx* ctx, const erp_polish_inputs* in, const erp_winner* winners,
+                              bool from_winners, double valid_abs, float thr, int32_t rounds,
+                              erp_polish_result* d_out, erp_polish_round* d_rounds,
+                              uint8_t* d_mask, void* stream) {
     if (!ctx || !in || !(thr > 0) || rounds < 0 || rounds > kPolishMaxRounds || in->n_pairs < 0 ||
-        in->iters < 1 || in->key_stride < 0)
+        (!from_winners && in->iters < 1) || in->key_stride < 0)
         return ERP_INVALID_ARG;
     if (in->n_pairs == 0) return ERP_OK;
-    if (!d_out || !in->results || !in->hyps || !in->width || !in->height ||
-        (in->key_stride > 0 && (!in->key_left || !in->key_right)))
+    if (!d_out || !in->results || !(from_winners ? (const void*)winners : (const void*)in->hyps) ||
+        !in->width || !in->height || (in->key_stride > 0 && (!in->key_left || !in->key_right)))
         return ERP_INVALID_ARG;
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
@@ -358,8 +346,24 @@ erp_status erp_polish_dev(erp_ctx* ctx, const erp_polish_inputs* in, double vali
     a.out = d_out;
     a.rounds_out = rounds > 0 ? d_rounds : nullptr;
     a.mask = d_mask;
+    a.winners = from_winners ? winners : nullptr;
     ERP_LAUNCH_S(polish_kernel, dim3((unsigned)in->n_pairs), dim3(kPolishThreads), 0, st, a);
     return hipGetLastError() == hipSuccess ? ERP_OK : ERP_HIP_ERROR;
+}
+
+erp_status erp_polish_dev(erp_ctx* ctx, const erp_polish_inputs* in, double valid_abs, float thr,
+                          int32_t rounds, erp_polish_result* d_out, erp_polish_round* d_rounds,
+                          uint8_t* d_mask, void* stream) {
+    return polish_call(ctx, in, nullptr, false, valid_abs, thr, rounds, d_out, d_rounds, d_mask,
+                       stream);
+}
+
+erp_status erp_polish_winners_dev(erp_ctx* ctx, const erp_polish_inputs* in,
+                                  const erp_winner* d_winners, double valid_abs, float thr,
+                                  int32_t rounds, erp_polish_result* d_out,
+                                  erp_polish_round* d_rounds, uint8_t* d_mask, void* stream) {
+    return polish_call(ctx, in, d_winners, true, valid_abs, thr, rounds, d_out, d_rounds, d_mask,
+                       stream);
 }
 
 erp_status erp_eight_point_find_polished(erp_ctx* ctx, int32_t W, int32_t H,

@@ -34,6 +34,12 @@ public:
                        std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out,
                        int match_size, float thr, int rounds,
                        std::vector<uint8_t>* inlier_mask = nullptr);
+    // find plus the winning iteration's record (erp_match.h "winner records"; no reference
+    // counterpart): winner.E is the solved 9-vector R_vec_out / T_vec_out were decomposed from,
+    // e.g. for an epipolar drawing of the returned pose.  Draws from the stream as find does.
+    void find_winner(int im_width, int im_height, std::vector<KeyPoint>& key_left,
+                     std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out,
+                     int match_size, erp_winner& winner);
     // src/eight_point.hpp:15-19
     void eight_point_estimation(int im_width, int im_height, std::vector<Point3d>& key_point_left_rect,
                                 std::vector<Point3d>& key_point_right_rect, Vec3f& R1_vec,

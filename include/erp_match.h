@@ -192,7 +192,8 @@ erp_status erp_ctx_reserve(erp_ctx* ctx, int32_t n_pairs, int32_t max_nq, int32_
    stream holds (seed, draws consumed, the 31-word glibc window); attached to a context
    (erp_ctx_set_rand_stream) it replaces cfg->seed / cfg->offset in the CONSUMING calls:
        erp_eight_point_find, erp_eight_point_find_dev, erp_initial_guess, erp_pair_batch_run,
-       erp_image_pairs_run (and erp_epipolar_draw_dev, which shuffles on it);
+       erp_image_pairs_run, their *_winner(s) forms (and erp_epipolar_draw_dev, which shuffles
+       on it);
    these ignore cfg->seed and cfg->offset, draw from the stream and advance it.  NOT consuming:
    erp_eight_point_hypotheses_dev and the erp_consensus_* calls, which reproduce blocks of a
    larger find at an explicit offset and stay on cfg->offset.  ERP_SAMPLER_PHILOX on a context
@@ -524,6 +525,64 @@ erp_status erp_eight_point_find_polished(erp_ctx* ctx, int32_t W, int32_t H,
                                          int32_t m, const erp_ransac_cfg* cfg, float thr,
                                          int32_t rounds, erp_pair_result* h_result,
                                          erp_polish_result* h_polish, uint8_t* h_mask);
+
+/* ---- winner records: the winning iteration's E without hypothesis records ----
+   find returns R and T but not the essential matrix they came from; the per-iteration records
+   (out->hyps, 120 B per iteration) carry it, and the lite route exists to avoid exactly their
+   traffic.  The winner stage runs behind the consensus, one workgroup per pair: it finds the
+   iteration whose record pushed row min_idx (R1 then R2 per record, src/eight_point.cpp:
+   113-126) from the run's own validity flags, rebuilds that iteration's Gram from the sampler's
+   selection words still in the context's scratch (the Gram is an exact integer sum, so any order
+   gives the pipeline's 36 doubles), solves it by the pipeline's own path (thin Jacobi below 9
+   rows, inverse iteration, its Jacobi fallback) and writes E: byte for byte erp_hypothesis.E of
+   the same run with records.  Before it writes, it re-runs the estimate on that E and compares
+   the chosen rotation and T with the result record's R, T byte for byte: any mismatch (or a
+   min_idx that names no row) gives the record status ERP_INTERNAL, never a plausible matrix.
+   A pair whose result status is not ERP_OK gets that status and zeros.  The stage allocates
+   nothing, synchronises nothing, uses no atomics and draws no rand(). */
+typedef struct erp_winner {      /* 88 bytes */
+    int32_t status;              /* the pair's erp_status; not ERP_OK: the rest is zero */
+    int32_t iter;                /* the iteration whose record pushed row min_idx */
+    int32_t which;               /* 0: the row is that iteration's R1, 1: its R2 */
+    int32_t sample_n;            /* rows of the sample that was re-solved */
+    double E[9];                 /* the solved 9-vector of that iteration: byte for byte
+                                    erp_hypothesis.E of the same run with records */
+} erp_winner;
+/* erp_pair_batch_run followed by the winner stage into d_winners [n_pairs] (device, required),
+   on the records route when out->hyps is given (or cfg->inlier_thr > 0) and on the lite route
+   otherwise; results and every other output are erp_pair_batch_run's.  A consuming call on a
+   rand stream exactly as erp_pair_batch_run is.  With erp_ctx_set_graphs on, this call still
+   enqueues plainly (kernel by kernel), as erp_pair_batch_run does under stage timing; the
+   winner stage is not timed by erp_ctx_set_profiling.  ERP_INVALID_ARG when d_winners is NULL
+   or ERP_OPT_DEBUG_STAGES is not -1 (a skipped stage group would leave another call's scratch
+   under the re-solve). */
+erp_status erp_pair_batch_run_winners(erp_ctx* ctx, const erp_pair_batch* batch, float ratio,
+                                      const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
+                                      erp_winner* d_winners, void* stream);
+/* erp_eight_point_find_dev followed by the winner stage: d_hyps may be NULL (the lite route),
+   d_winner [1] is required.  ERP_OPT_DEBUG_STAGES as above. */
+erp_status erp_eight_point_find_winner_dev(erp_ctx* ctx, int32_t W, int32_t H,
+                                           const erp_point2f* d_kl, const erp_point2f* d_kr,
+                                           int32_t m, const erp_ransac_cfg* cfg,
+                                           erp_pair_result* d_result, erp_hypothesis* d_hyps,
+                                           erp_winner* d_winner, void* stream);
+/* host pointers, synchronous: erp_eight_point_find plus the winner record (h_winner required;
+   R_out, T_out, h_result may be NULL).  Returns the find's status. */
+erp_status erp_eight_point_find_winner(erp_ctx* ctx, int32_t W, int32_t H,
+                                       const erp_point2f* h_kl, const erp_point2f* h_kr,
+                                       int32_t m, const erp_ransac_cfg* cfg, float R_out[3],
+                                       float T_out[3], erp_pair_result* h_result,
+                                       erp_winner* h_winner);
+/* erp_polish_dev with steps 1-2 of its rules taken from winner records: winner_iter,
+   winner_which and e_0 are d_winners[p]'s iter, which and E; in->hyps and in->iters are not
+   read.  A winner status that is not ERP_OK is handled like a result status that is not ERP_OK
+   (step 7; the result's status comes first).  Everything else is erp_polish_dev's: given the
+   winners and results of one run, the outputs are byte-identical to erp_polish_dev on that
+   run's records. */
+erp_status erp_polish_winners_dev(erp_ctx* ctx, const erp_polish_inputs* in,
+                                  const erp_winner* d_winners, double valid_abs, float thr,
+                                  int32_t rounds, erp_polish_result* d_out,
+                                  erp_polish_round* d_rounds, uint8_t* d_mask, void* stream);
 
 /* ---- ERP remaps around the hot path ----
    Images are 8-bit 3-channel (CV_8UC3, BGR) H x W x 3, row-major, device pointers.  Output
