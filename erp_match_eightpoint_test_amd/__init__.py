@@ -26,7 +26,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi, synth
-from .capi import (DMATCH_DTYPE, HYP_DTYPE, POLISH_DTYPE, POLISH_ROUND_DTYPE, RESULT_DTYPE,
+from .capi import (DMATCH_DTYPE, HYP_DTYPE, POLISH_DTYPE, POLISH_ROUND_DTYPE, POSE_DTYPE, RESULT_DTYPE,
                    WINNER_DTYPE, Context, ErpError, RandStream, check, default_cfg,
                    process_rand_stream)
 
@@ -34,7 +34,8 @@ __all__ = ["feature_matcher", "eight_point", "erp_rotation", "spherical_surf", "
            "PairBatchRunner", "Context", "ErpError", "RandStream", "process_rand_stream",
            "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "POLISH_DTYPE",
            "POLISH_ROUND_DTYPE", "WINNER_DTYPE", "results_to_numpy", "hyps_to_numpy",
-           "polish_to_numpy", "polish_rounds_to_numpy", "winners_to_numpy", "sweep_relative_rotation", "synth", "capi"]
+           "polish_to_numpy", "polish_rounds_to_numpy", "winners_to_numpy", "sweep_relative_rotation", "synth", "capi",
+           "POSE_DTYPE", "pose_to_numpy"]
 
 
 def _np_ptr(a: np.ndarray):
@@ -177,6 +178,7 @@ class eight_point:  # noqa: N801  (reference class name)
         self.last_result = None
         self.last_polish = None
         self.last_winner = None
+        self.last_pose = None
         if stream is not None:
             self.ctx.set_rand_stream(stream)
 
@@ -249,6 +251,38 @@ class eight_point:  # noqa: N801  (reference class name)
         self.last_polish = np.frombuffer(bytes(pol), POLISH_DTYPE)[0]
         check(st, "find_polished")
         return self.last_polish["R"].copy(), self.last_polish["T"].copy(), mask[:m].astype(bool)
+
+    def find_posed(self, im_width: int, im_height: int, key_left, key_right, thr: float,
+                   rounds: int = 3, min_sin2: float = 0.0, match_size: int | None = None):
+        """find, the polish and the pose selection (erp_eight_point_find_posed; no reference
+        counterpart): the cheirality vote over (R1 | R2) x (+t | -t) on the polish's E and inlier
+        set -> (R (3,), T (3,), inlier_mask (match_size,) bool, depth (match_size, 2) float64,
+        front (match_size,) bool).  R, T are the pose record's: the reference's candidates made
+        definite.  ``last_result`` is find's record, ``last_polish`` the polish's, ``last_pose``
+        the pose record (POSE_DTYPE; its status is ERP_TOO_FEW_POINTS when no match could vote).
+        Consumes a rand stream exactly as find does."""
+        kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
+        kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
+        m = kl.shape[0] if match_size is None else int(match_size)
+        if m > kl.shape[0] or m > kr.shape[0]:
+            raise ValueError("match_size larger than the keypoint arrays")
+        kl = np.ascontiguousarray(kl[:m])
+        kr = np.ascontiguousarray(kr[:m])
+        res, pol, pose = capi.PairResult(), capi.PolishResult(), capi.Pose()
+        mask = np.zeros(max(m, 1), np.uint8)
+        front = np.zeros(max(m, 1), np.uint8)
+        depth = np.zeros((max(m, 1), 2), np.float64)
+        st = self.ctx.L.erp_eight_point_find_posed(self.ctx.h, im_width, im_height, _np_ptr(kl),
+                                                   _np_ptr(kr), m, C.byref(self.cfg), thr,
+                                                   int(rounds), float(min_sin2), C.byref(res),
+                                                   C.byref(pol), C.byref(pose), _np_ptr(mask),
+                                                   _np_ptr(depth), _np_ptr(front))
+        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
+        self.last_polish = np.frombuffer(bytes(pol), POLISH_DTYPE)[0]
+        self.last_pose = np.frombuffer(bytes(pose), POSE_DTYPE)[0]
+        check(st, "find_posed")
+        return (self.last_pose["R"].copy(), self.last_pose["T"].copy(), mask[:m].astype(bool),
+                depth[:m], front[:m].astype(bool))
 
     def initial_guess(self, im_width: int, im_height: int, key_point_left_rect,
                       key_point_right_rect, match_size: int | None = None):
@@ -1072,6 +1106,35 @@ class PairBatchRunner:
                                valid_abs=self.cfg.valid_abs, want_rounds=want_rounds,
                                stream=stream, winners=None if use_hyps else out["winners"])
 
+    def select_pose(self, out: dict, width, height, source: str = "winners", polish: dict | None = None,
+                    thr: float = 0.0, min_sin2: float = 0.0,
+                    want=("depth", "front", "results"), stream=None) -> dict:
+        """The pose selection (include/erp_match.h "pose selection"; no reference counterpart) on
+        the dict ``run(..., want=("winners", "key_left", "key_right"))`` returned: the cheirality
+        vote over (R1 | R2) x (+t | -t) per pair.  source="winners": on the winners' E, every
+        match with |l^T E' r| < thr voting (thr <= 0: every match); source="polish": on the E
+        and the inlier mask of ``polish`` (what polish() returned; thr is normally 0 then).
+        -> {"pose": records (pose_to_numpy), "depth": float64 [P, max_nq, 2], "front": uint8
+        [P, max_nq], "results": the result records with the selected R, T (they feed
+        rectify_batch(results=...))}.  One launch on torch's current stream (or ``stream``);
+        ``out`` and ``polish`` are only read."""
+        need = ["results", "key_left", "key_right"] + (["winners"] if source == "winners" else [])
+        missing = [k for k in need if k not in out]
+        if missing:
+            raise ValueError(f"select_pose needs run(..., want=('winners', 'key_left', "
+                             f"'key_right')): missing {missing}")
+        if source == "winners":
+            src, e_off, s_off, mask = out["winners"], 16, 0, None
+        elif source == "polish":
+            if polish is None or "polish" not in polish or "mask" not in polish:
+                raise ValueError("select_pose(source='polish') needs polish=polish(...) with its mask")
+            src, e_off, s_off, mask = polish["polish"], 48, 24, polish["mask"]
+        else:
+            raise ValueError("select_pose: source is 'winners' or 'polish'")
+        return self.ctx.select_pose(out["results"], out["key_left"], out["key_right"], width,
+                                    height, src, e_off, s_off, mask=mask, thr=thr,
+                                    min_sin2=min_sin2, want=want, stream=stream)
+
     def _launch(self, b, ratio, outs, stream, dev):
         import torch
         o = capi.BatchOutputs(*[outs[k].data_ptr() if k in outs else None
@@ -1101,6 +1164,11 @@ def polish_to_numpy(t) -> np.ndarray:
 def winners_to_numpy(t) -> np.ndarray:
     """erp_winner records (run(..., want=("winners",)) "winners") -> [P]"""
     return t.cpu().numpy().view(WINNER_DTYPE).reshape(-1)
+
+
+def pose_to_numpy(t) -> np.ndarray:
+    """erp_pose records (Context.select_pose / PairBatchRunner.select_pose "pose") -> [P]"""
+    return t.cpu().numpy().view(POSE_DTYPE).reshape(-1)
 
 
 def polish_rounds_to_numpy(t) -> np.ndarray:

@@ -91,6 +91,20 @@ class Winner(C.Structure):
                 ("sample_n", C.c_int32), ("E", C.c_double * 9)]
 
 
+class Pose(C.Structure):
+    _fields_ = [("status", C.c_int32), ("which", C.c_int32), ("t_sign", C.c_int32),
+                ("n_voters", C.c_int32), ("votes", C.c_int32 * 4), ("rot_agrees", C.c_int32),
+                ("t_flipped", C.c_int32), ("R", C.c_float * 3), ("T", C.c_float * 3),
+                ("Rm", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class PoseInputs(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("reserved", C.c_int32), ("key_stride", C.c_int64),
+                ("key_left", P), ("key_right", P), ("width", P), ("height", P), ("results", P),
+                ("e", P), ("e_stride", C.c_int64), ("src_status", P),
+                ("src_status_stride", C.c_int64), ("mask", P)]
+
+
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"),
                          ("distance", "<f4")])
 HYP_DTYPE = np.dtype([("R1", "<f4", 3), ("R2", "<f4", 3), ("T", "<f4", 3), ("R1_valid", "<i4"),
@@ -108,7 +122,13 @@ POLISH_DTYPE = np.dtype([("R", "<f4", 3), ("T", "<f4", 3), ("status", "<i4"),
                         align=True)
 WINNER_DTYPE = np.dtype([("status", "<i4"), ("iter", "<i4"), ("which", "<i4"), ("sample_n", "<i4"),
                          ("E", "<f8", 9)], align=True)
+POSE_DTYPE = np.dtype([("status", "<i4"), ("which", "<i4"), ("t_sign", "<i4"), ("n_voters", "<i4"),
+                       ("votes", "<i4", 4), ("rot_agrees", "<i4"), ("t_flipped", "<i4"),
+                       ("R", "<f4", 3), ("T", "<f4", 3), ("Rm", "<f8", 9), ("t", "<f8", 3)],
+                      align=True)
 POLISH_MAX_ROUNDS = 8
+assert POSE_DTYPE.itemsize == C.sizeof(Pose) == 160
+assert C.sizeof(PoseInputs) == 96
 assert WINNER_DTYPE.itemsize == C.sizeof(Winner) == 88
 assert DMATCH_DTYPE.itemsize == C.sizeof(DMatch) == 16
 assert POLISH_ROUND_DTYPE.itemsize == C.sizeof(PolishRound) == 112
@@ -143,7 +163,7 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_rectify_batch_dev", "erp_rectify_results_dev", "erp_rectify_matrices_results",
             "erp_polish_dev", "erp_eight_point_find_polished", "erp_pair_batch_run_winners",
             "erp_eight_point_find_winner_dev", "erp_eight_point_find_winner",
-            "erp_polish_winners_dev"]
+            "erp_polish_winners_dev", "erp_pose_select_dev", "erp_eight_point_find_posed"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -326,6 +346,11 @@ def load(build_if_missing: bool = False):
                                               C.POINTER(RansacCfg), P, P, P, P]
     L.erp_polish_winners_dev.argtypes = [P, C.POINTER(PolishInputs), P, C.c_double, C.c_float,
                                          C.c_int32, P, P, P, P]
+    L.erp_pose_select_dev.argtypes = [P, C.POINTER(PoseInputs), C.c_float, C.c_double, P, P, P, P,
+                                      P]
+    L.erp_eight_point_find_posed.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
+                                             C.POINTER(RansacCfg), C.c_float, C.c_int32,
+                                             C.c_double, P, P, P, P, P, P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]
@@ -492,6 +517,61 @@ class Context:
                   "erp_polish_winners_dev")
         else:
             check(self.L.erp_polish_dev(self.h, C.byref(inp), *tail), "erp_polish_dev")
+        return out
+
+    def select_pose(self, results, key_left, key_right, width, height, source, e_offset: int,
+                    status_offset: int | None = None, mask=None, thr: float = 0.0,
+                    min_sin2: float = 0.0, want=("depth", "front", "results"),
+                    stream=None) -> dict:
+        """erp_pose_select_dev on torch CUDA tensors: results [P, 64] uint8, key_left / key_right
+        [P, stride, 2] float32, width / height [P] int32, source = uint8 [P, record bytes] records
+        that hold each pair's solved 9-vector at byte ``e_offset`` and (``status_offset``) its
+        int32 status -- winner records (16, 0) or polish records (48, 24) --, mask uint8 [P,
+        stride] or None -> {"pose": uint8 [P, 160] (POSE_DTYPE), "depth": float64 [P, stride, 2],
+        "front": uint8 [P, stride], "results": uint8 [P, 64]} (the last three as ``want`` names
+        them).  Asynchronous on ``stream`` (default: torch's current stream)."""
+        import torch
+        chk = [(results, torch.uint8), (source, torch.uint8), (key_left, torch.float32),
+               (key_right, torch.float32), (width, torch.int32), (height, torch.int32)]
+        if mask is not None:
+            chk.append((mask, torch.uint8))
+        for t, dt in chk:
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
+                    not t.is_contiguous():
+                raise ValueError("select_pose: inputs must be contiguous CUDA tensors of the C "
+                                 "types")
+        n = results.shape[0]
+        if results.dim() != 2 or results.shape[1] != RESULT_DTYPE.itemsize or source.dim() != 2 or \
+                source.shape[0] != n or e_offset < 0 or e_offset + 72 > source.shape[1] or \
+                (status_offset is not None and not 0 <= status_offset <= source.shape[1] - 4) or \
+                key_left.shape != key_right.shape or key_left.dim() != 3 or \
+                key_left.shape[0] != n or key_left.shape[2] != 2 or width.numel() != n or \
+                height.numel() != n or \
+                (mask is not None and tuple(mask.shape) != tuple(key_left.shape[:2])):
+            raise ValueError("select_pose: results [P, 64], source [P, bytes], keys [P, stride, 2], "
+                             "width / height [P], mask [P, stride] expected")
+        unknown = [k for k in want if k not in ("depth", "front", "results")]
+        if unknown:
+            raise ValueError(f"select_pose: unknown outputs {unknown}")
+        dev = results.device
+        stride, rec = key_left.shape[1], source.shape[1]
+        inp = PoseInputs(n, 0, stride, key_left.data_ptr(), key_right.data_ptr(),
+                         width.data_ptr(), height.data_ptr(), results.data_ptr(),
+                         source.data_ptr() + e_offset, rec,
+                         None if status_offset is None else source.data_ptr() + status_offset,
+                         rec, None if mask is None else mask.data_ptr())
+        out = {"pose": torch.empty((n, POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
+        if "depth" in want:
+            out["depth"] = torch.empty((n, stride, 2), dtype=torch.float64, device=dev)
+        if "front" in want:
+            out["front"] = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+        if "results" in want:
+            out["results"] = torch.empty((n, RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
+        check(self.L.erp_pose_select_dev(self.h, C.byref(inp), thr, min_sin2, ptr("pose"),
+                                         ptr("depth"), ptr("front"), ptr("results"), st),
+              "erp_pose_select_dev")
         return out
 
     def stage_times(self) -> dict:

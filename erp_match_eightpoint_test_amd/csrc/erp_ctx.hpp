@@ -47,6 +47,9 @@ enum CtxSlot {
     // polish.hip: the device side of erp_eight_point_find_polished (hypothesis records, polish
     // record, W / H, mask)
     kSlotPolishHost,
+    // pose.hip: the device side of erp_eight_point_find_posed (result, winner, polish and pose
+    // records, W / H, depths, mask, front)
+    kSlotPoseHost,
     kCtxSlotCount
 };
 

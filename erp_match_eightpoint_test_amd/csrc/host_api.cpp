@@ -115,6 +115,33 @@ void eight_point::find_polished(int W, int H, std::vector<KeyPoint>& kl, std::ve
     }
 }
 
+void eight_point::find_posed(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
+                             Vec3f& R, Vec3f& T, int match_size, float thr, int rounds,
+                             double min_sin2, std::vector<uint8_t>* inlier_mask,
+                             std::vector<double>* depth, std::vector<uint8_t>* front) {
+    if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
+        throw error(ERP_INVALID_ARG, "find_posed: match_size");
+    std::vector<erp_point2f> a((size_t)match_size), b((size_t)match_size);
+    for (int i = 0; i < match_size; i++) {
+        a[i] = erp_point2f{kl[i].pt.x, kl[i].pt.y};
+        b[i] = erp_point2f{kr[i].pt.x, kr[i].pt.y};
+    }
+    if (inlier_mask) inlier_mask->assign((size_t)match_size, 0);
+    if (depth) depth->assign((size_t)match_size * 2, 0.0);
+    if (front) front->assign((size_t)match_size, 0);
+    const bool any = match_size > 0;
+    check(erp_eight_point_find_posed(ctx_, W, H, a.data(), b.data(), match_size, &cfg, thr, rounds,
+                                     min_sin2, &last_, &last_polish_, &last_pose_,
+                                     inlier_mask && any ? inlier_mask->data() : nullptr,
+                                     depth && any ? depth->data() : nullptr,
+                                     front && any ? front->data() : nullptr),
+          "find_posed");
+    for (int k = 0; k < 3; k++) {
+        R[k] = last_pose_.R[k];
+        T[k] = last_pose_.T[k];
+    }
+}
+
 void eight_point::initial_guess(int, int, std::vector<Point3d>& l, std::vector<Point3d>& r, Vec3f& R,
                                 Vec3f& T, int match_size) {
     if (match_size < 0 || (size_t)match_size > l.size() || (size_t)match_size > r.size())

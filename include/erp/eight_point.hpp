@@ -34,6 +34,17 @@ public:
                        std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out,
                        int match_size, float thr, int rounds,
                        std::vector<uint8_t>* inlier_mask = nullptr);
+    // find, the polish and the pose selection (erp_match.h "pose selection"; no reference
+    // counterpart): the cheirality vote over (R1 | R2) x (+t | -t) on the polish's E and inlier
+    // set.  R_vec_out / T_vec_out: the pose record's -- the reference's candidates made definite
+    // (zeros when no match could vote: last_pose().status is then ERP_TOO_FEW_POINTS).
+    // inlier_mask, depth ((d_l, d_r) per match) and front (may be nullptr) are resized to
+    // match_size (depth: 2 * match_size).  Draws from the stream as find does.
+    void find_posed(int im_width, int im_height, std::vector<KeyPoint>& key_left,
+                    std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out,
+                    int match_size, float thr, int rounds, double min_sin2 = 0.0,
+                    std::vector<uint8_t>* inlier_mask = nullptr,
+                    std::vector<double>* depth = nullptr, std::vector<uint8_t>* front = nullptr);
     // find plus the winning iteration's record (erp_match.h "winner records"; no reference
     // counterpart): winner.E is the solved 9-vector R_vec_out / T_vec_out were decomposed from,
     // e.g. for an epipolar drawing of the returned pose.  Draws from the stream as find does.
@@ -59,11 +70,13 @@ public:
     erp_ransac_cfg cfg;                 // reference constants (erp_ransac_cfg_default)
     const erp_pair_result& last_result() const { return last_; }
     const erp_polish_result& last_polish() const { return last_polish_; }
+    const erp_pose& last_pose() const { return last_pose_; }
 
 private:
     erp_ctx* ctx_ = nullptr;
     erp_pair_result last_{};
     erp_polish_result last_polish_{};
+    erp_pose last_pose_{};
 };
 
 }  // namespace erp

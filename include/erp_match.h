@@ -584,6 +584,110 @@ erp_status erp_polish_winners_dev(erp_ctx* ctx, const erp_polish_inputs* in,
                                   int32_t rounds, erp_polish_result* d_out,
                                   erp_polish_round* d_rounds, uint8_t* d_mask, void* stream);
 
+/* ---- pose selection: the cheirality vote over (R1 | R2) x (+t | -t), with depths ----
+   No reference counterpart; opt-in.  decomposeEssentialMat gives two rotations and a translation
+   of arbitrary sign; the reference keeps whichever rotation has every Euler angle under 1.57 rad
+   (src/eight_point.cpp:70-84) and never decides the sign of T, so find's answer is half a pose
+   and a rotation above 90 degrees on an axis cannot be returned at all.  This stage makes the
+   decision every essential-matrix user expects (OpenCV: recoverPose): it triangulates the
+   matches under the four candidates and keeps the one that puts the points in front of both
+   cameras -- on the sphere "in front" is a positive depth along both bearings, so all four
+   candidates are testable.  R and T of the record are the reference's (R1 | R2, +-t) made
+   definite, not new quantities.  It is a stage behind find, the winner records and the polish:
+   it reads what they wrote and changes none of it, draws no rand(), allocates nothing,
+   synchronises nothing and uses no atomics.
+   Per pair, from its result record (status, M, R, T), a solved 9-vector e, its gathered matched
+   keypoints, W, H, an optional byte mask, thr and min_sin2 >= 0; all arithmetic fp64, products
+   and sums evaluated left to right as written (the library is built with contraction off):
+   1. Candidates.  E' = the rank-2 correction of e (:45-50); (R1, R2, t) = decompose_e(E')
+      (cv::decomposeEssentialMat).  Candidate k = 2 * which + s has the rotation Rc = which ? R2
+      : R1 and the translation tc = s ? -t : t.  The model is the one decomposeEssentialMat
+      inverts, E' = [t]x R with the residual l^T E' r:  d_l * l = d_r * (Rc r) + tc,  d_l and d_r
+      the depths along the left and the right bearing in units of the baseline.
+   2. Per match i < M: l, r = the bearings as find computes them (:163-186).  For each of R1 and
+      R2: q = Rc r (q_i = Rc[i][0] r_0 + Rc[i][1] r_1 + Rc[i][2] r_2);  a = l.l, b = l.q,
+      c = q.q, lt = l.t, qt = q.t (x.y = x_0 y_0 + x_1 y_1 + x_2 y_2);  det = a*c - b*b (the
+      squared sine of the parallax);  d_l = (c*lt - b*qt) / det,  d_r = (b*lt - a*qt) / det.
+      Under -t both depths change sign exactly, so they are computed once per rotation.
+   3. Voters.  Match i votes if the mask is NULL or mask[i] != 0;  thr <= 0 or
+      |l^T E' r| < thr (the residual in the fixed order given at erp_ransac_cfg.inlier_thr, thr
+      widened from float);  and, for the rotation in question, det > 0 and det >= min_sin2.  It
+      votes for (Rc, +t) if d_l > 0 && d_r > 0 and for (Rc, -t) if d_l < 0 && d_r < 0.  n_voters
+      counts the matches that pass the mask and threshold tests and the parallax test for at
+      least one rotation.
+   4. Selection.  The candidate with the most votes wins, the lowest k on a tie.  n_voters == 0
+      gives the pose status ERP_TOO_FEW_POINTS and zeros (n_voters and votes are kept: all 0).
+   5. The record erp_pose, below.
+   6. Optional outputs: depth (d_l, d_r) under the selected pose (both negated when t_sign is
+      -1) for the matches that pass rule 3's tests for the selected rotation, 0 elsewhere;
+      front = 1 where the match voted for the selected candidate;  results_out = the result
+      records with R and T replaced by the pose's where the POSE's status is ERP_OK, every other
+      byte (and every byte of the other records) copied: it feeds erp_rectify_results_dev as it
+      is.  depth and front are 0 from M up to key_stride.
+   7. Status rules are the polish's step 7: a result status that is not ERP_OK, or a source
+      status that is not ERP_OK (the result's comes first), gives that status and zeros -- not an
+      error of the call.  An M above key_stride counts as key_stride, a negative one as 0; a
+      pair with more than 65535 matches gets ERP_INVALID_ARG.
+   8. The outputs of a pair do not depend on the other pairs of the call and are bit-identical
+      from run to run.  The stage is not timed by erp_ctx_set_profiling. */
+typedef struct erp_pose {        /* 160 bytes */
+    int32_t status;      /* the pair's erp_status; not ERP_OK: the rest is zero */
+    int32_t which;       /* 0: the selected rotation is decompose_e's R1, 1: its R2 */
+    int32_t t_sign;      /* +1: the selected translation is decompose_e's t, -1: -t */
+    int32_t n_voters;
+    int32_t votes[4];    /* votes[k], k = 2 * which + (t_sign < 0) */
+    int32_t rot_agrees;  /* 1: R below equals the result record's R byte for byte */
+    int32_t t_flipped;   /* 1: (double)T[0] T_res[0] + .. [1] + .. [2] (left to right) < 0, T_res
+                            the result record's T: the selected T is the result's negated */
+    float R[3];          /* rot2eular of Rm (XYZ Euler, rad), narrowed */
+    float T[3];          /* t, narrowed */
+    double Rm[9];        /* the selected rotation matrix, row-major */
+    double t[3];         /* the selected translation tc (unit) */
+} erp_pose;
+/* device pointers.  n_pairs .. results as in erp_polish_inputs.  e: pair p's solved 9-vector is
+   the 9 doubles at (char*)e + p * e_stride (8-byte aligned, e_stride a multiple of 8);
+   src_status (may be NULL): pair p's int32 source status at (char*)src_status + p *
+   src_status_stride.  From winner records: e = &d_winners[0].E, e_stride = 88, src_status =
+   &d_winners[0].status, src_status_stride = 88, with a thr > 0; from the polish: e =
+   &d_polish[0].E, src_status = &d_polish[0].status, both strides 120, mask = the polish's mask
+   and thr <= 0. */
+typedef struct erp_pose_inputs {
+    int32_t n_pairs;
+    int32_t reserved;               /* 0 */
+    int64_t key_stride;             /* keypoint (and mask) slots per pair */
+    const erp_point2f* key_left;    /* [n_pairs][key_stride] */
+    const erp_point2f* key_right;   /* [n_pairs][key_stride] */
+    const int32_t* width;           /* [n_pairs] */
+    const int32_t* height;          /* [n_pairs] */
+    const erp_pair_result* results; /* [n_pairs] */
+    const void* e;
+    int64_t e_stride;
+    const void* src_status;         /* may be NULL */
+    int64_t src_status_stride;
+    const uint8_t* mask;            /* [n_pairs][key_stride]; may be NULL */
+} erp_pose_inputs;
+/* device pointers, asynchronous on `stream`, no device-to-host copy and no synchronisation: one
+   launch, one workgroup per pair.  d_out [n_pairs]; d_depth [n_pairs][key_stride][2] doubles,
+   d_front [n_pairs][key_stride] bytes and d_results_out [n_pairs] may each be NULL (d_results_out
+   may be in->results itself).  n_pairs == 0: ERP_OK, nothing is done.  min_sin2 < 0, a NaN thr
+   or min_sin2, key_stride < 0 or a misaligned e: ERP_INVALID_ARG before any GPU work.  The call
+   allocates nothing. */
+erp_status erp_pose_select_dev(erp_ctx* ctx, const erp_pose_inputs* in, float thr, double min_sin2,
+                               erp_pose* d_out, double* d_depth, uint8_t* d_front,
+                               erp_pair_result* d_results_out, void* stream);
+/* host pointers, synchronous: erp_eight_point_find with its winner record on the lite route,
+   then erp_polish_winners_dev with thr (> 0) and rounds (0..8), then the selection on the
+   polish's E and mask (no residual test of its own: the mask is the polish's inlier set).  A
+   consuming call on a rand stream exactly as erp_eight_point_find is; a call that fails on thr,
+   rounds or min_sin2 consumes nothing.  h_result, h_polish, h_pose, h_mask [m], h_depth [m][2]
+   and h_front [m] may be NULL.  Returns the find's status (h_pose->status is the pose's). */
+erp_status erp_eight_point_find_posed(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* h_kl,
+                                      const erp_point2f* h_kr, int32_t m,
+                                      const erp_ransac_cfg* cfg, float thr, int32_t rounds,
+                                      double min_sin2, erp_pair_result* h_result,
+                                      erp_polish_result* h_polish, erp_pose* h_pose,
+                                      uint8_t* h_mask, double* h_depth, uint8_t* h_front);
+
 /* ---- ERP remaps around the hot path ----
    Images are 8-bit 3-channel (CV_8UC3, BGR) H x W x 3, row-major, device pointers.  Output
    pixels whose inverse-warped source falls outside the image are NOT written (the reference
