@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -355,6 +356,29 @@ bool cfg_ok(const erp_ransac_cfg* cfg) {
            cfg->sample_frac > 0 &&
            cfg->sample_frac <= 1.0 && cfg->trim_lo >= 0 && cfg->trim_hi <= 1.0 &&
            cfg->trim_lo <= cfg->trim_hi && cfg->inlier_thr >= 0.0f && cfg->inlier_thr < 1e30f;
+}
+
+// caller bearings (erp_initial_guess, erp_eight_point_estimation): every component finite
+bool bearings_finite(const double* b, int32_t m) {
+    for (size_t k = 0; k < (size_t)m * 3; k++)
+        if (!std::isfinite(b[k])) return false;
+    return true;
+}
+
+// erp_initial_guess's bearing scale (include/erp_match.h).  The Gram pass holds
+// the products (l_a l_b)(r_c r_d) 2^44 in six balanced base-256 digits, |product| < 7.97.  With
+// c = the largest |component| of one side, that side is multiplied by 2^-e: e = 0 when
+// 0.5 <= c <= 1.5 (unit bearings: 0.577 <= c <= 1, so they reach the device byte for byte),
+// otherwise the e with 0.5 <= c 2^-e < 1.  Both sides then have c <= 1.5 and every product is
+// below 1.5^4 = 5.07.  A power of two is exact and scales the Gram by a power of two: the solved
+// vector, R and T are those of the caller's bearings.  c == 0 (no rows, or all zero): e = 0.
+int bearing_side_exponent(const double* b, int32_t m) {
+    double c = 0.0;
+    for (size_t k = 0; k < (size_t)m * 3; k++) c = std::max(c, std::fabs(b[k]));
+    if (c == 0.0 || (c >= 0.5 && c <= 1.5)) return 0;
+    int e = 0;
+    std::frexp(c, &e);  // c = f 2^e, 0.5 <= f < 1
+    return e;
 }
 
 // the Philox sampler's per-lane LDS bitmap holds M <= 20480 positions (kernels.hip
@@ -1195,6 +1219,8 @@ erp_status erp_initial_guess(erp_ctx* ctx, const double* h_bl, const double* h_b
     if (!ctx || m < 0 || m > 65535 || (m > 0 && (!h_bl || !h_br)) || !cfg_ok(cfg) ||
         !sampler_m_ok(cfg, m))
         return ERP_INVALID_ARG;
+    if (!bearings_finite(h_bl, m) || !bearings_finite(h_br, m)) return ERP_INVALID_ARG;
+    const int el = bearing_side_exponent(h_bl, m), er = bearing_side_exponent(h_br, m);
     erp_pair_result r;
     {
         ERP_CK(hipSetDevice(ctx->device));
@@ -1208,8 +1234,8 @@ erp_status erp_initial_guess(erp_ctx* ctx, const double* h_bl, const double* h_b
         std::vector<double> pts((size_t)(m + 1) * 6, 0.0);
         for (int32_t i = 0; i < m; i++)
             for (int k = 0; k < 3; k++) {
-                pts[(size_t)i * 6 + k] = h_bl[(size_t)i * 3 + k];
-                pts[(size_t)i * 6 + 3 + k] = h_br[(size_t)i * 3 + k];
+                pts[(size_t)i * 6 + k] = std::ldexp(h_bl[(size_t)i * 3 + k], -el);
+                pts[(size_t)i * 6 + 3 + k] = std::ldexp(h_br[(size_t)i * 3 + k], -er);
             }
         ERP_CK(hipMemcpy(ctx->pts.p, pts.data(), (size_t)(m + 1) * 48, hipMemcpyHostToDevice));
         ERP_CK(hipMemcpy(ctx->counts.p, &m, 4, hipMemcpyHostToDevice));
@@ -1230,6 +1256,7 @@ erp_status erp_eight_point_estimation(erp_ctx* ctx, const double* h_bl, const do
                                       int32_t m, erp_hypothesis* h_out) {
     if (!ctx || m < 0 || !h_out || (m > 0 && (!h_bl || !h_br))) return ERP_INVALID_ARG;
     if (m < 1) return ERP_TOO_FEW_POINTS;
+    if (!bearings_finite(h_bl, m) || !bearings_finite(h_br, m)) return ERP_INVALID_ARG;
     ERP_CK(hipSetDevice(ctx->device));
     HostCtxCall call(ctx);
     if (!ensure(ctx->in_d, (size_t)m * 48 + 36 * 8 * 2 + sizeof(erp_hypothesis) + 64))

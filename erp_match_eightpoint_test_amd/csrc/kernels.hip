@@ -1202,6 +1202,7 @@ constexpr int kGramLimbs = 6;
 constexpr int kGramTiles = 7;                 // 32-column MFMA tiles
 constexpr int kGramN = kGramTiles * 32;
 constexpr double kGramScale = 0x1p44;
+constexpr double kGramMaxQ = 0x1.fp46;        // 7.75 2^44: below the six digits' range
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
@@ -1261,7 +1262,14 @@ __global__ __launch_bounds__(256) void gram_limbs_kernel(const int32_t* __restri
         const int ai = a < 3 ? 0 : (a < 5 ? 1 : 2), aj = a < 3 ? a : (a < 5 ? a - 2 : 2);
         const int ei = e < 3 ? 0 : (e < 5 ? 1 : 2), ej = e < 3 ? e : (e < 5 ? e - 2 : 2);
         const double LL = pr[ai] * pr[aj], RR = pr[3 + ei] * pr[3 + ej];
-        long long q = __double2ll_rn((LL * RR) * kGramScale);
+        // six balanced base-256 digits hold |q| < 7.97 2^44.  A product outside kGramMaxQ -- a
+        // NaN or Inf bearing (a non-finite keypoint) or a bearing far from unit length -- would
+        // be converted with an unspecified result or wrap: the pair gets ERP_INVALID_ARG
+        // (consensus_final_kernel) and the digits of that entry are zero
+        const double v = (LL * RR) * kGramScale;
+        const bool ok = __builtin_fabs(v) < kGramMaxQ;  // false for NaN
+        if (!ok) atomicOr(&flags[p], 8);
+        long long q = __double2ll_rn(ok ? v : 0.0);
 #pragma unroll
         for (int k = 0; k < kGramLimbs; k++) {
             const int d = (int)(int8_t)(q & 0xff);

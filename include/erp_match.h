@@ -91,7 +91,12 @@ typedef struct erp_ransac_cfg {
     double sample_frac;  /* 0.25 :102 */
     double trim_lo;      /* 0.2  :143 */
     double trim_hi;      /* 0.8  :143 */
-    double valid_abs;    /* 1.57 :76,81 */
+    double valid_abs;    /* 1.57 :76,81.  A rotation is valid when every |Euler angle| < valid_abs,
+                            so valid_abs <= 0 or NaN makes none valid: every pair that reaches
+                            the consensus gets K = 0 and ERP_NO_VALID_HYPOTHESIS (the hypothesis
+                            records are still written, every flag 0) -- accepted, not an
+                            ERP_INVALID_ARG.  valid_abs > pi makes every finite rotation valid:
+                            K = 2 iters */
     uint32_t seed;       /* 1: the reference never calls srand() */
     float inlier_thr;    /* 0 (default) = off: nothing below changes.  > 0: every iteration also
                             counts its inliers, the correspondences with |l^T E' r| < inlier_thr
@@ -374,7 +379,36 @@ erp_status erp_match_two_image(erp_ctx* ctx, const float* h_desc1, int32_t n1,
                                const float* h_desc2, int32_t n2, int32_t dim,
                                erp_dmatch* h_out, int32_t* h_count);
 
-/* ---- estimator (eight_point::find / eight_point_estimation) ---- */
+/* ---- estimator (eight_point::find / eight_point_estimation) ----
+   Input domain (tests/test_gpu_estimator_domain.py pins every rule):
+   Keypoints may lie anywhere, on the image or outside it (the poles, negative or far-outside
+   pixels): pixel -> bearing (src/eight_point.cpp:163-186) is periodic and gives unit bearings.
+   NON-FINITE KEYPOINTS.  A pair with a NaN or Inf coordinate in a MATCHED keypoint (any of its M
+   rows, sampled or not) gets the per-pair status ERP_INVALID_ARG with R = T = 0, min_idx = -1 --
+   in erp_eight_point_find / _find_dev and their winner, polished and posed forms, and per pair
+   in erp_pair_batch_run (the other pairs of the batch are computed as if it were not there,
+   byte for byte); the winner, polish and pose records of the pair carry the status and zeros.
+   A deliberate difference from the reference, which turns the pixel into NaN bearings, gets a NaN
+   E from every iteration that sampled the row, finds both rotations invalid and so silently
+   answers from the remaining iterations: here the status is loud, never ERP_OK with some K.
+   The Gram pass sets the flag where it quantises the bearings' products; the same test refuses
+   any product outside its fixed point (below), so nothing is converted or wrapped unseen.
+   NON-FINITE BEARINGS.  erp_initial_guess and erp_eight_point_estimation return ERP_INVALID_ARG
+   from a host check when a bearing component is NaN or Inf (no GPU work, no rand() drawn).
+   BEARING SCALE.  The estimate is invariant under a scale of either side (the reference's SVD of
+   A is; the oracle exactly so).  find's bearings are unit vectors.  erp_eight_point_estimation
+   computes its Gram in fp64 and takes the caller's bearings as they are.  erp_initial_guess
+   computes the Grams in fixed point: the products (l_a l_b)(r_c r_d) 2^44, rounded, in six
+   balanced base-256 digits, which hold |product| < 7.97.  So it brings each side into the window
+   first, on the host, by an exact power of two: with c = the largest |component| of a side over
+   all m rows, the side is multiplied by 2^-e, e = 0 when 0.5 <= c <= 1.5 -- unit bearings
+   (0.577 <= c <= 1) reach the device byte for byte -- and otherwise the e with
+   0.5 <= c 2^-e < 1 (c = 0: e = 0).  Every product is then below 1.5^4 = 5.07; the Gram is
+   scaled by a power of two, which leaves its eigenvectors, R and T alone: bearings times 2,
+   1e-4, 1e3 or 2^40, and sides scaled differently, give the result of the unit bearings.  The
+   scale is one factor per side, not per row: rows much shorter than the longest lose digits
+   (a product below 2^-45 rounds to 0), so a row 1e-3 of the longest hardly counts, while row
+   lengths within a factor 4 of each other keep the parity bars. */
 /* device pointers: m matched keypoint pairs -> result (R, T, diagnostics). */
 erp_status erp_eight_point_find_dev(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* d_kl,
                                     const erp_point2f* d_kr, int32_t m, const erp_ransac_cfg* cfg,
@@ -419,11 +453,14 @@ erp_status erp_eight_point_find(erp_ctx* ctx, int32_t W, int32_t H, const erp_po
                                 const erp_point2f* h_kr, int32_t m, const erp_ransac_cfg* cfg,
                                 float R_out[3], float T_out[3], erp_pair_result* h_result);
 /* host pointers, synchronous: initial_guess on m bearing pairs (m x 3 doubles each), i.e. find
-   after the pixel->bearing step (src/eight_point.cpp:87-150). */
+   after the pixel->bearing step (src/eight_point.cpp:87-150).  The bearings need not be unit
+   vectors: each side is scaled by an exact power of two into the fixed point's window, and a
+   non-finite component gives ERP_INVALID_ARG ("Input domain" above). */
 erp_status erp_initial_guess(erp_ctx* ctx, const double* h_bl, const double* h_br, int32_t m,
                              const erp_ransac_cfg* cfg, float R_out[3], float T_out[3],
                              erp_pair_result* h_result);
-/* host pointers, synchronous: one eight_point_estimation on m bearing pairs (m x 3 doubles). */
+/* host pointers, synchronous: one eight_point_estimation on m bearing pairs (m x 3 doubles), any
+   finite scale (fp64 Gram); a non-finite component gives ERP_INVALID_ARG. */
 erp_status erp_eight_point_estimation(erp_ctx* ctx, const double* h_bl, const double* h_br,
                                       int32_t m, erp_hypothesis* h_out);
 

@@ -326,9 +326,10 @@ def _batch(pairs, device="cuda"):
             int(np.diff(ol).max()), int(np.diff(orr).max()))
 
 
-def _check_batch_vs_oracle(oracle, pairs, outs, iters):
+def _check_batch_vs_oracle(oracle, pairs, outs, iters, cfg=None):
     """outs = PairBatchRunner.run(..., want=("matches", "hyps", "samples", "rvec", "dist")) of
-    pairs, synchronised: every stage against the oracle"""
+    pairs, synchronised: every stage against the oracle (cfg: the oracle's, for a run with
+    other constants than the reference's; its iters = iters)"""
     from erp_match_eightpoint_test_amd import hyps_to_numpy, results_to_numpy
     res = results_to_numpy(outs["results"])
     hyps = hyps_to_numpy(outs["hyps"])
@@ -340,7 +341,7 @@ def _check_batch_vs_oracle(oracle, pairs, outs, iters):
         assert np.array_equal(got.view(np.uint32).reshape(-1), ref.view(np.uint32).reshape(-1))
         kl = p["kp_l"][ref["queryIdx"]]
         kr = p["kp_r"][ref["trainIdx"]]
-        o = oracle.find(p["W"], p["H"], kl, kr, oracle.make_cfg(iters=iters), detail=True)
+        o = oracle.find(p["W"], p["H"], kl, kr, cfg or oracle.make_cfg(iters=iters), detail=True)
         s = o["sample_n"]
         got_s = np.sort(outs["samples"][i, :, :s].cpu().numpy(), axis=1)
         assert np.array_equal(got_s, np.sort(o["samples"], axis=1))
