@@ -77,6 +77,32 @@ class feature_matcher:  # noqa: N801  (reference class name)
               "match_two_image")
         return out[:n.value].copy()
 
+    def match_guided(self, descriptor1, descriptor2, key1, key2, im_width: int, im_height: int,
+                     E, thr: float = 0.003, ratio: float = 0.8, max_dist: float = 0.0,
+                     unique: bool = True):
+        """Guided matching (include/erp_match.h "guided matching"; no reference counterpart):
+        descriptor1 rows rematched among the descriptor2 rows whose keypoint lies in the
+        epipolar band |l^T E' r| < thr of the solved 9-vector E (E' its rank-2 correction), kept
+        when d0 < ratio * d1 inside the band (and d0 < max_dist when max_dist > 0; ``unique``:
+        one query per train row) -> DMatch array, ascending queryIdx.  Host arrays, one pair,
+        synchronous (erp_match_guided)."""
+        q = np.ascontiguousarray(descriptor1, np.float32)
+        t = np.ascontiguousarray(descriptor2, np.float32)
+        k1, k2 = _keys_host(key1), _keys_host(key2)
+        e = np.ascontiguousarray(E, np.float64).reshape(-1)
+        if q.ndim != 2 or t.ndim != 2 or q.shape[1] != 64 or t.shape[1] != 64 or \
+                len(k1) != q.shape[0] or len(k2) != t.shape[0] or e.size != 9:
+            raise ValueError("match_guided: descriptors [n, 64] with one keypoint per row and a "
+                             "9-element E expected")
+        out = np.zeros(max(q.shape[0], 1), DMATCH_DTYPE)
+        n = C.c_int32(0)
+        cfg = capi.GuidedCfg(thr, ratio, max_dist, 1 if unique else 0)
+        check(self.ctx.L.erp_match_guided(self.ctx.h, _np_ptr(q), q.shape[0], _np_ptr(t),
+                                          t.shape[0], _np_ptr(k1), _np_ptr(k2), im_width,
+                                          im_height, _np_ptr(e), C.byref(cfg), _np_ptr(out),
+                                          C.byref(n)), "match_guided")
+        return out[:n.value].copy()
+
     # ---- SURF (src/feature_matcher.cpp:26-40, xfeatures2d::SURF::create() defaults) ----
     def surf(self, images, max_kp: int = 16384, **params):
         """detect_key_point + comput_descriptor on CUDA uint8 images [n, H, W] (gray) or
@@ -1134,6 +1160,41 @@ class PairBatchRunner:
         return self.ctx.select_pose(out["results"], out["key_left"], out["key_right"], width,
                                     height, src, e_off, s_off, mask=mask, thr=thr,
                                     min_sin2=min_sin2, want=want, stream=stream)
+
+    def guided_match(self, out: dict, desc_l, desc_r, kp_l, kp_r, off_l, off_r, width, height,
+                     max_nq: int, max_nt: int | None = None, *, source: str = "winners",
+                     polish: dict | None = None, thr: float, ratio: float = 0.8,
+                     max_dist: float = 0.0, unique: bool = True,
+                     want=("matches", "key_left", "key_right", "gated", "results", "winners"),
+                     stream=None) -> dict:
+        """Guided matching (include/erp_match.h "guided matching"; no reference counterpart)
+        behind ``run(..., want=("winners", ...))`` on the same packed batch: every pair's
+        descriptors rematched inside the epipolar band |l^T E' r| < thr of its solved E, with
+        the ratio test d0 < ratio * d1 inside the band.  source="winners": the E of out["winners"];
+        source="polish": the E of ``polish`` (what polish() returned).  -> {"results", "winners",
+        "key_left", "key_right", "matches", "count", "gated"} (``want`` names all but count):
+        results = out's records with M replaced by the guided count and winners = records that
+        carry E, so polish() and select_pose() take the returned dict as they take run()'s.  Three
+        launches on torch's current stream (or ``stream``); ``out`` and ``polish`` are only read.
+        max_nt=None reads the largest right row count from off_r (a device-to-host copy)."""
+        if max_nt is None:
+            max_nt = int((off_r[1:] - off_r[:-1]).max().item()) if off_r.numel() > 1 else 0
+        if "results" not in out:
+            raise ValueError("guided_match needs run()'s dict with its results")
+        if source == "winners":
+            if "winners" not in out:
+                raise ValueError("guided_match(source='winners') needs run(..., want=('winners',))")
+            src, e_off, s_off = out["winners"], 16, 0
+        elif source == "polish":
+            if polish is None or "polish" not in polish:
+                raise ValueError("guided_match(source='polish') needs polish=polish(...)")
+            src, e_off, s_off = polish["polish"], 48, 24
+        else:
+            raise ValueError("guided_match: source is 'winners' or 'polish'")
+        return self.ctx.guided_match(desc_l, desc_r, kp_l, kp_r, off_l, off_r, width, height,
+                                     max_nq, max_nt, src, e_off, s_off, results=out["results"],
+                                     thr=thr, ratio=ratio, max_dist=max_dist, unique=unique,
+                                     want=want, stream=stream)
 
     def _launch(self, b, ratio, outs, stream, dev):
         import torch

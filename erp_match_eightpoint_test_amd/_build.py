@@ -20,9 +20,11 @@ ARCH = os.environ.get("ERP_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip", "surf.hip", "surf_api.hip", "viz.hip",
            "image_batch.hip", "rand_stream.hip", "sweep.hip", "polish.hip", "winner.hip", "pose.hip",
+           "guided.hip",
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
-           "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp", "erp_ctx.hpp", "erp_winner.hpp"]
+           "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp", "erp_ctx.hpp", "erp_winner.hpp",
+           "erp_l2.hpp"]
 PUBLIC_HEADERS = ["erp_match.h", os.path.join("erp", "feature_matcher.hpp"),
                   os.path.join("erp", "eight_point.hpp"), os.path.join("erp", "rand_stream.hpp")]
 
@@ -121,6 +123,9 @@ WINNER_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "winner_driver")
 # erp::eight_point::find_posed
 POSE_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "pose_driver.cpp")
 POSE_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "pose_driver")
+# erp::feature_matcher::match_guided
+GUIDED_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "guided_driver.cpp")
+GUIDED_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "guided_driver")
 
 
 def _build_cpp_driver(src: str, out: str, force: bool) -> str:
@@ -138,11 +143,13 @@ def build_driver(force: bool = False) -> str:
     """the C++ class-API drivers (tests/cpp): host code only, g++ against liberp_match.so -- the
     link a reference maintainer would do.  Returns the class API
     driver; build_stream_driver() the rand stream one, build_polish_driver() the polish one,
-    build_winner_driver() the winner one, build_pose_driver() the pose one."""
+    build_winner_driver() the winner one, build_pose_driver() the pose one,
+    build_guided_driver() the guided matching one."""
     _build_cpp_driver(STREAM_DRIVER_SRC, STREAM_DRIVER_BIN, force)
     _build_cpp_driver(POLISH_DRIVER_SRC, POLISH_DRIVER_BIN, force)
     _build_cpp_driver(WINNER_DRIVER_SRC, WINNER_DRIVER_BIN, force)
     _build_cpp_driver(POSE_DRIVER_SRC, POSE_DRIVER_BIN, force)
+    _build_cpp_driver(GUIDED_DRIVER_SRC, GUIDED_DRIVER_BIN, force)
     return _build_cpp_driver(DRIVER_SRC, DRIVER_BIN, force)
 
 
@@ -160,6 +167,10 @@ def build_winner_driver(force: bool = False) -> str:
 
 def build_pose_driver(force: bool = False) -> str:
     return _build_cpp_driver(POSE_DRIVER_SRC, POSE_DRIVER_BIN, force)
+
+
+def build_guided_driver(force: bool = False) -> str:
+    return _build_cpp_driver(GUIDED_DRIVER_SRC, GUIDED_DRIVER_BIN, force)
 
 
 if __name__ == "__main__":

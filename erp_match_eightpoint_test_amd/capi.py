@@ -105,6 +105,21 @@ class PoseInputs(C.Structure):
                 ("src_status_stride", C.c_int64), ("mask", P)]
 
 
+class GuidedCfg(C.Structure):
+    _fields_ = [("thr", C.c_float), ("ratio", C.c_float), ("max_dist", C.c_float),
+                ("unique", C.c_int32)]
+
+
+class GuidedInputs(C.Structure):
+    _fields_ = [("batch", PairBatch), ("results", P), ("e", P), ("e_stride", C.c_int64),
+                ("src_status", P), ("src_status_stride", C.c_int64)]
+
+
+class GuidedOutputs(C.Structure):
+    _fields_ = [("count", P), ("matches", P), ("key_left", P), ("key_right", P), ("gated", P),
+                ("results_out", P), ("winners_out", P)]
+
+
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"),
                          ("distance", "<f4")])
 HYP_DTYPE = np.dtype([("R1", "<f4", 3), ("R2", "<f4", 3), ("T", "<f4", 3), ("R1_valid", "<i4"),
@@ -129,6 +144,8 @@ POSE_DTYPE = np.dtype([("status", "<i4"), ("which", "<i4"), ("t_sign", "<i4"), (
 POLISH_MAX_ROUNDS = 8
 assert POSE_DTYPE.itemsize == C.sizeof(Pose) == 160
 assert C.sizeof(PoseInputs) == 96
+assert C.sizeof(GuidedCfg) == 16 and C.sizeof(GuidedInputs) == 120 and \
+    C.sizeof(GuidedOutputs) == 56
 assert WINNER_DTYPE.itemsize == C.sizeof(Winner) == 88
 assert DMATCH_DTYPE.itemsize == C.sizeof(DMatch) == 16
 assert POLISH_ROUND_DTYPE.itemsize == C.sizeof(PolishRound) == 112
@@ -163,7 +180,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_rectify_batch_dev", "erp_rectify_results_dev", "erp_rectify_matrices_results",
             "erp_polish_dev", "erp_eight_point_find_polished", "erp_pair_batch_run_winners",
             "erp_eight_point_find_winner_dev", "erp_eight_point_find_winner",
-            "erp_polish_winners_dev", "erp_pose_select_dev", "erp_eight_point_find_posed"]
+            "erp_polish_winners_dev", "erp_pose_select_dev", "erp_eight_point_find_posed",
+            "erp_match_guided_dev", "erp_match_guided"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -351,6 +369,10 @@ def load(build_if_missing: bool = False):
     L.erp_eight_point_find_posed.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
                                              C.POINTER(RansacCfg), C.c_float, C.c_int32,
                                              C.c_double, P, P, P, P, P, P]
+    L.erp_match_guided_dev.argtypes = [P, C.POINTER(GuidedInputs), C.POINTER(GuidedCfg),
+                                       C.POINTER(GuidedOutputs), P]
+    L.erp_match_guided.argtypes = [P, P, C.c_int32, P, C.c_int32, P, P, C.c_int32, C.c_int32, P,
+                                   C.POINTER(GuidedCfg), P, P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]
@@ -572,6 +594,67 @@ class Context:
         check(self.L.erp_pose_select_dev(self.h, C.byref(inp), thr, min_sin2, ptr("pose"),
                                          ptr("depth"), ptr("front"), ptr("results"), st),
               "erp_pose_select_dev")
+        return out
+
+    GUIDED_WANT = ("matches", "key_left", "key_right", "gated", "results", "winners")
+
+    def guided_match(self, desc_l, desc_r, kp_l, kp_r, off_l, off_r, width, height, max_nq: int,
+                     max_nt: int, source, e_offset: int, status_offset: int | None = None,
+                     results=None, thr: float = 0.003, ratio: float = 0.8, max_dist: float = 0.0,
+                     unique: bool = True, want=GUIDED_WANT, stream=None) -> dict:
+        """erp_match_guided_dev on torch CUDA tensors: the packed batch as PairBatchRunner.run
+        takes it, source = uint8 [P, record bytes] records that hold each pair's solved 9-vector
+        at byte ``e_offset`` and (``status_offset``) its int32 status -- winner records (16, 0)
+        or polish records (48, 24) --, results uint8 [P, 64] or None (every pair counts as ok)
+        -> {"count": int32 [P], "matches": int32 [P, max_nq, 4] (DMatch rows), "key_left" /
+        "key_right": float32 [P, max_nq, 2], "gated": int64 [P], "results": uint8 [P, 64] (M
+        replaced), "winners": uint8 [P, 88]} (all but count as ``want`` names them).
+        Asynchronous on ``stream`` (default: torch's current stream)."""
+        import torch
+        chk = [(desc_l, torch.float32), (desc_r, torch.float32), (kp_l, torch.float32),
+               (kp_r, torch.float32), (off_l, torch.int64), (off_r, torch.int64),
+               (width, torch.int32), (height, torch.int32), (source, torch.uint8)]
+        if results is not None:
+            chk.append((results, torch.uint8))
+        for t, dt in chk:
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
+                    not t.is_contiguous():
+                raise ValueError("guided_match: inputs must be contiguous CUDA tensors of the C "
+                                 "types")
+        n = off_l.shape[0] - 1
+        if off_r.shape[0] != n + 1 or width.numel() != n or height.numel() != n or \
+                source.dim() != 2 or source.shape[0] != n or e_offset < 0 or \
+                e_offset + 72 > source.shape[1] or desc_l.dim() != 2 or desc_r.dim() != 2 or \
+                (status_offset is not None and not 0 <= status_offset <= source.shape[1] - 4) or \
+                (results is not None and tuple(results.shape) != (n, RESULT_DTYPE.itemsize)):
+            raise ValueError("guided_match: off_l / off_r [P + 1], width / height [P], source "
+                             "[P, bytes], results [P, 64] expected")
+        unknown = [k for k in want if k not in self.GUIDED_WANT]
+        if unknown or ("results" in want and results is None):
+            raise ValueError(f"guided_match: unknown outputs {unknown}, or 'results' without "
+                             "result records")
+        dev, rec = desc_l.device, source.shape[1]
+        inp = GuidedInputs(
+            PairBatch(n, desc_l.shape[1], max_nq, max_nt, desc_l.data_ptr(), desc_r.data_ptr(),
+                      kp_l.data_ptr(), kp_r.data_ptr(), off_l.data_ptr(), off_r.data_ptr(),
+                      width.data_ptr(), height.data_ptr()),
+            None if results is None else results.data_ptr(), source.data_ptr() + e_offset, rec,
+            None if status_offset is None else source.data_ptr() + status_offset, rec)
+        shapes = {"matches": ((n, max_nq, 4), torch.int32),
+                  "key_left": ((n, max_nq, 2), torch.float32),
+                  "key_right": ((n, max_nq, 2), torch.float32), "gated": ((n,), torch.int64),
+                  "results": ((n, RESULT_DTYPE.itemsize), torch.uint8),
+                  "winners": ((n, WINNER_DTYPE.itemsize), torch.uint8)}
+        out = {"count": torch.empty((n,), dtype=torch.int32, device=dev)}
+        for k in want:
+            out[k] = torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev)
+        ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
+        o = GuidedOutputs(ptr("count"), ptr("matches"), ptr("key_left"), ptr("key_right"),
+                          ptr("gated"), ptr("results"), ptr("winners"))
+        cfg = GuidedCfg(thr, ratio, max_dist, 1 if unique else 0)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        check(self.L.erp_match_guided_dev(self.h, C.byref(inp), C.byref(cfg), C.byref(o), st),
+              "erp_match_guided_dev")
         return out
 
     def stage_times(self) -> dict:

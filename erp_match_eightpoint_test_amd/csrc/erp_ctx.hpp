@@ -50,6 +50,9 @@ enum CtxSlot {
     // pose.hip: the device side of erp_eight_point_find_posed (result, winner, polish and pose
     // records, W / H, depths, mask, front)
     kSlotPoseHost,
+    // guided.hip: the per-query (j0, e0, e1, |G_i|) records, the per-train-row 64-bit claim
+    // words, the train bearings with each pair's E', and the device side of erp_match_guided
+    kSlotGuidedQuery, kSlotGuidedClaim, kSlotGuidedBearings, kSlotGuidedHost,
     kCtxSlotCount
 };
 

@@ -22,16 +22,52 @@ feature_matcher::~feature_matcher() {
     if (ctx_) erp_ctx_destroy(ctx_);
 }
 
+// the rows of d back to back (d itself when it is packed already)
+static const float* pack(const Descriptors& d, std::vector<float>& buf) {
+    const size_t row = (size_t)d.cols * sizeof(float);
+    if (d.step == 0 || d.step == row) return d.data;
+    buf.resize((size_t)d.rows * d.cols);
+    for (int r = 0; r < d.rows; r++)
+        memcpy(&buf[(size_t)r * d.cols], (const char*)d.data + (size_t)r * d.step, row);
+    return buf.data();
+}
+
+static std::vector<DMatch> to_dmatches(const std::vector<erp_dmatch>& out, int32_t n) {
+    std::vector<DMatch> res((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        res[i].queryIdx = out[i].queryIdx;
+        res[i].trainIdx = out[i].trainIdx;
+        res[i].imgIdx = out[i].imgIdx;
+        res[i].distance = out[i].distance;
+    }
+    return res;
+}
+
+std::vector<DMatch> feature_matcher::match_guided(const Descriptors& d1, const Descriptors& d2,
+                                                  const std::vector<KeyPoint>& key1,
+                                                  const std::vector<KeyPoint>& key2, int im_width,
+                                                  int im_height, const double E[9], float thr,
+                                                  float ratio, float max_dist, bool unique) {
+    if (d1.cols != 64 || d2.cols != 64 || d1.rows < 0 || d2.rows < 0 ||
+        key1.size() != (size_t)d1.rows || key2.size() != (size_t)d2.rows)
+        throw error(ERP_INVALID_ARG, "match_guided: descriptors [n][64] with one keypoint per row");
+    std::vector<float> b1, b2;
+    const float* p1 = pack(d1, b1);
+    const float* p2 = pack(d2, b2);
+    std::vector<erp_point2f> k1(key1.size()), k2(key2.size());
+    for (size_t i = 0; i < key1.size(); i++) k1[i] = erp_point2f{key1[i].pt.x, key1[i].pt.y};
+    for (size_t i = 0; i < key2.size(); i++) k2[i] = erp_point2f{key2[i].pt.x, key2[i].pt.y};
+    std::vector<erp_dmatch> out((size_t)std::max(d1.rows, 1));
+    int32_t n = 0;
+    const erp_guided_cfg cfg{thr, ratio, max_dist, unique ? 1 : 0};
+    check(erp_match_guided(ctx_, p1, d1.rows, p2, d2.rows, k1.data(), k2.data(), im_width,
+                           im_height, E, &cfg, out.data(), &n),
+          "match_guided");
+    return to_dmatches(out, n);
+}
+
 std::vector<DMatch> feature_matcher::match_two_image(const Descriptors& d1, const Descriptors& d2) {
     if (d1.cols != d2.cols) throw error(ERP_INVALID_ARG, "match_two_image: descriptor size");
-    auto pack = [](const Descriptors& d, std::vector<float>& buf) -> const float* {
-        const size_t row = (size_t)d.cols * sizeof(float);
-        if (d.step == 0 || d.step == row) return d.data;
-        buf.resize((size_t)d.rows * d.cols);
-        for (int r = 0; r < d.rows; r++)
-            memcpy(&buf[(size_t)r * d.cols], (const char*)d.data + (size_t)r * d.step, row);
-        return buf.data();
-    };
     std::vector<float> b1, b2;
     const float* p1 = pack(d1, b1);
     const float* p2 = pack(d2, b2);
@@ -44,14 +80,7 @@ std::vector<DMatch> feature_matcher::match_two_image(const Descriptors& d1, cons
         s = ERP_INVALID_ARG;  // the host entry point fixes the reference ratio
     }
     check(s, "match_two_image");
-    std::vector<DMatch> res((size_t)n);
-    for (int32_t i = 0; i < n; i++) {
-        res[i].queryIdx = out[i].queryIdx;
-        res[i].trainIdx = out[i].trainIdx;
-        res[i].imgIdx = out[i].imgIdx;
-        res[i].distance = out[i].distance;
-    }
-    return res;
+    return to_dmatches(out, n);
 }
 
 eight_point::eight_point(int device) {

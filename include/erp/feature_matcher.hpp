@@ -28,6 +28,16 @@ public:
     // descriptor2 rows, kept when d0 < 0.3f * d1; ascending queryIdx.
     std::vector<DMatch> match_two_image(const Descriptors& descriptor1, const Descriptors& descriptor2);
 
+    // Guided matching (erp_match.h "guided matching"; no reference counterpart): descriptor1 rows
+    // rematched among the descriptor2 rows whose keypoint lies in the epipolar band
+    // |l^T E' r| < thr of the solved 9-vector E, kept when d0 < ratio * d1 inside the band (and
+    // d0 < max_dist when max_dist > 0; unique: one query per train row); ascending queryIdx.
+    std::vector<DMatch> match_guided(const Descriptors& descriptor1, const Descriptors& descriptor2,
+                                     const std::vector<KeyPoint>& key1,
+                                     const std::vector<KeyPoint>& key2, int im_width, int im_height,
+                                     const double E[9], float thr, float ratio = 0.8f,
+                                     float max_dist = 0.0f, bool unique = true);
+
     float ratio_thresh = 0.3f;  // src/feature_matcher.cpp:47
 
 private:

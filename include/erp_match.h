@@ -725,6 +725,96 @@ erp_status erp_eight_point_find_posed(erp_ctx* ctx, int32_t W, int32_t H, const 
                                       erp_polish_result* h_polish, erp_pose* h_pose,
                                       uint8_t* h_mask, double* h_depth, uint8_t* h_front);
 
+/* ---- guided matching: the descriptors rematched inside the epipolar band of a solved E ----
+   No reference counterpart; opt-in.  match_two_image keeps a query when d0 < 0.3 * d1 over ALL
+   train rows (src/feature_matcher.cpp:42-59): nothing but descriptor distance is known before the
+   geometry is.  Once an essential matrix is solved, the candidates of a query can be restricted
+   to the train keypoints near its epipolar line, and a much looser ratio is safe there.  The
+   stage runs behind find, the winner records and the polish: it reads a packed batch
+   (erp_pair_batch), result records and a solved 9-vector per pair and changes none of them.
+   Per pair p of the batch (dim 64; nq = its left rows, nt = its right rows), from its result
+   record, e at (e, e_stride) and an optional source status at (src_status, src_status_stride),
+   both addressed as in erp_pose_inputs, and erp_guided_cfg; arithmetic as stated (the library is
+   built with contraction off):
+   1. E' = the rank-2 correction of e (src/eight_point.cpp:45-50).  l_i, i < nq, and r_j,
+      j < nt, are the bearings of the left and right keypoints as find computes them
+      (:163-186).
+   2. Gate.  G_i = { j : |l_i^T E' r_j| < thr }, the fp64 residual in the fixed order given at
+      erp_ransac_cfg.inlier_thr, thr widened from float.  A NaN residual (a non-finite keypoint)
+      is not gated and changes no status.  A guided match is therefore an inlier of the polish's
+      rule 4 at the same thr and E, bit for bit.
+   3. Distances.  e(i, j) = the squared distance in the flann::L2<float> order (the matcher's),
+      d = sqrtf(e).  j0 = the j of G_i with the smallest e, the lowest j among equal e;
+      d0 = d(i, j0); d1 = the smallest d over G_i without j0 (it may equal d0), +inf when
+      |G_i| = 1.
+   4. Query i is accepted when |G_i| >= 1, d0 < ratio * d1 (the float product of the matcher's
+      ratio test; true against +inf) and (max_dist <= 0 or d0 < max_dist).
+   5. unique != 0: among the accepted queries with the same j0 only the one with the smallest d0
+      stays, the lowest i among equal d0.
+   6. Outputs, each optional but count: count[p] = M_g, the queries that stay;  matches
+      [n_pairs][max_nq] in ascending queryIdx (pair-local indices, imgIdx 0, distance = d0);
+      key_left / key_right [n_pairs][max_nq], the keypoints of those matches;  gated [n_pairs]
+      (int64) = the sum over i of |G_i|;  results_out [n_pairs] = the result record with M
+      replaced by M_g and every other byte copied (it may be the input itself);  winners_out
+      [n_pairs] = an erp_winner with the pair's status, iter -1, which 0, sample_n 0 and E = e.
+      With results_out, winners_out and the gathered keys, erp_polish_winners_dev and
+      erp_pose_select_dev run on the guided list unchanged (the polish only copies iter and
+      which).  matches and keys are zero from M_g up to max_nq.
+   7. Status rules are the pose selection's rule 7: a result status that is not ERP_OK, or a
+      source status that is not ERP_OK (the result's comes first), gives count 0, gated 0, zero
+      matches and keys, M = 0 in results_out and a winners_out record with that status and zeros
+      -- not an error of the call.  nq = 0 or nt = 0 gives count 0 with ERP_OK.  dim != 64,
+      thr <= 0 or NaN, ratio <= 0 or NaN, a NaN max_dist, a misaligned e or max_nq > 65535 (as
+      erp_pair_batch_run refuses it) give ERP_INVALID_ARG before any GPU work.
+   8. The outputs of a pair do not depend on the other pairs of the call and are bit-identical
+      from run to run: the only atomics are a 64-bit integer min (rule 5) and a 64-bit integer
+      add (gated), whose results do not depend on the order.  The stage draws no rand(), never
+      touches a rand stream and synchronises nothing; it is not timed by erp_ctx_set_profiling.
+   Consequence: |l^T E' r| <= 0.7072 for unit bearings and a unit-norm e, so thr = 1 gates
+   every finite pair (i, j); with unique = 0 and max_dist = 0 the list is then, for nt >= 2,
+   erp_match_knn2_ratio's at the same ratio, bit for bit. */
+typedef struct erp_guided_cfg {
+    float thr;           /* > 0: the gate, as erp_ransac_cfg.inlier_thr */
+    float ratio;         /* > 0: d0 < ratio * d1 */
+    float max_dist;      /* <= 0: off; otherwise d0 < max_dist */
+    int32_t unique;      /* != 0: rule 5 */
+} erp_guided_cfg;
+/* device pointers.  batch: as erp_pair_batch_run reads it (max_nt bounds the right rows per
+   pair).  results may be NULL: every pair then counts as ERP_OK (and results_out must be NULL).
+   e / src_status: as in erp_pose_inputs (from winner records: &d_winners[0].E and .status, both
+   strides 88; from the polish: &d_polish[0].E and .status, both strides 120). */
+typedef struct erp_guided_inputs {
+    erp_pair_batch batch;
+    const erp_pair_result* results; /* [n_pairs]; may be NULL */
+    const void* e;
+    int64_t e_stride;
+    const void* src_status;         /* may be NULL */
+    int64_t src_status_stride;
+} erp_guided_inputs;
+typedef struct erp_guided_outputs {
+    int32_t* count;                 /* [n_pairs] (required) */
+    erp_dmatch* matches;            /* [n_pairs][max_nq] */
+    erp_point2f* key_left;          /* [n_pairs][max_nq] */
+    erp_point2f* key_right;         /* [n_pairs][max_nq] */
+    int64_t* gated;                 /* [n_pairs] */
+    erp_pair_result* results_out;   /* [n_pairs] */
+    erp_winner* winners_out;        /* [n_pairs] */
+} erp_guided_outputs;
+/* device pointers, asynchronous on `stream`, no device-to-host copy and no synchronisation:
+   three launches (bearings and E', gate and top-2, compaction).  n_pairs == 0: ERP_OK, nothing
+   is done.  The context's scratch for the stage (per query 16 bytes, per train row 48) grows on
+   the first call of a shape and is reused afterwards (erp_ctx_reserve does not cover it). */
+erp_status erp_match_guided_dev(erp_ctx* ctx, const erp_guided_inputs* in,
+                                const erp_guided_cfg* cfg, const erp_guided_outputs* out,
+                                void* stream);
+/* host pointers, synchronous, one pair, no result record: h_desc1 [n1][64], h_desc2 [n2][64],
+   h_kp1 [n1], h_kp2 [n2], E the solved 9-vector -> h_out [n1] (the first *h_count are valid).
+   n1 > 65535, W or H <= 0: ERP_INVALID_ARG. */
+erp_status erp_match_guided(erp_ctx* ctx, const float* h_desc1, int32_t n1, const float* h_desc2,
+                            int32_t n2, const erp_point2f* h_kp1, const erp_point2f* h_kp2,
+                            int32_t W, int32_t H, const double E[9], const erp_guided_cfg* cfg,
+                            erp_dmatch* h_out, int32_t* h_count);
+
 /* ---- ERP remaps around the hot path ----
    Images are 8-bit 3-channel (CV_8UC3, BGR) H x W x 3, row-major, device pointers.  Output
    pixels whose inverse-warped source falls outside the image are NOT written (the reference
