@@ -191,6 +191,22 @@ class feature_matcher:  # noqa: N801  (reference class name)
         return out[: int(cnt.item())]
 
 
+def _keys(key_left, key_right, match_size):
+    """-> (kl, kr, m): the first m = match_size (None: all of key_left) keypoints of each side
+    as contiguous float32 [m, 2]"""
+    kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
+    kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
+    m = kl.shape[0] if match_size is None else int(match_size)
+    if m > kl.shape[0] or m > kr.shape[0]:
+        raise ValueError("match_size larger than the keypoint arrays")
+    return np.ascontiguousarray(kl[:m]), np.ascontiguousarray(kr[:m]), m
+
+
+def _record(struct, dtype):
+    """a ctypes record as a numpy scalar of its structured dtype"""
+    return np.frombuffer(bytes(struct), dtype)[0]
+
+
 class eight_point:  # noqa: N801  (reference class name)
     """eight_point (src/eight_point.hpp:8-28).  ``cfg`` holds the reference constants.
     ``stream``: a RandStream that find / initial_guess draw from and advance, as the reference's
@@ -211,20 +227,14 @@ class eight_point:  # noqa: N801  (reference class name)
     def find(self, im_width: int, im_height: int, key_left, key_right, match_size: int | None = None):
         """-> (R_vec_out (3,) float32, T_vec_out (3,) float32); raises ErpError on the
         reference's undefined-behaviour cases (too few points, no valid hypothesis)."""
-        kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
-        kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
-        m = kl.shape[0] if match_size is None else int(match_size)
-        if m > kl.shape[0] or m > kr.shape[0]:
-            raise ValueError("match_size larger than the keypoint arrays")
-        kl = np.ascontiguousarray(kl[:m])
-        kr = np.ascontiguousarray(kr[:m])
+        kl, kr, m = _keys(key_left, key_right, match_size)
         R = np.zeros(3, np.float32)
         T = np.zeros(3, np.float32)
         res = capi.PairResult()
         st = self.ctx.L.erp_eight_point_find(self.ctx.h, im_width, im_height, _np_ptr(kl),
                                              _np_ptr(kr), m, C.byref(self.cfg), _np_ptr(R),
                                              _np_ptr(T), C.byref(res))
-        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
+        self.last_result = _record(res, RESULT_DTYPE)
         check(st, "find")
         return R, T
 
@@ -234,21 +244,15 @@ class eight_point:  # noqa: N801  (reference class name)
         reference counterpart) -> (R (3,), T (3,), E (3, 3) float64): E is the solved 9-vector
         R and T were decomposed from (sign arbitrary), e.g. for epipolar_tool.draw_epipole.
         ``last_winner`` is the record (WINNER_DTYPE: status, iter, which, sample_n, E)."""
-        kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
-        kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
-        m = kl.shape[0] if match_size is None else int(match_size)
-        if m > kl.shape[0] or m > kr.shape[0]:
-            raise ValueError("match_size larger than the keypoint arrays")
-        kl = np.ascontiguousarray(kl[:m])
-        kr = np.ascontiguousarray(kr[:m])
+        kl, kr, m = _keys(key_left, key_right, match_size)
         R = np.zeros(3, np.float32)
         T = np.zeros(3, np.float32)
         res, win = capi.PairResult(), capi.Winner()
         st = self.ctx.L.erp_eight_point_find_winner(self.ctx.h, im_width, im_height, _np_ptr(kl),
                                                     _np_ptr(kr), m, C.byref(self.cfg), _np_ptr(R),
                                                     _np_ptr(T), C.byref(res), C.byref(win))
-        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
-        self.last_winner = np.frombuffer(bytes(win), WINNER_DTYPE)[0]
+        self.last_result = _record(res, RESULT_DTYPE)
+        self.last_winner = _record(win, WINNER_DTYPE)
         check(st, "find_winner")
         check(int(self.last_winner["status"]), "find_winner: winner record")
         return R, T, self.last_winner["E"].reshape(3, 3).copy()
@@ -260,21 +264,15 @@ class eight_point:  # noqa: N801  (reference class name)
         them -> (R (3,), T (3,), inlier_mask (match_size,) bool) of the last accepted state.
         ``last_result`` is find's record (its R, T are find's answer), ``last_polish`` the
         polish record (POLISH_DTYPE).  Consumes a rand stream exactly as find does."""
-        kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
-        kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
-        m = kl.shape[0] if match_size is None else int(match_size)
-        if m > kl.shape[0] or m > kr.shape[0]:
-            raise ValueError("match_size larger than the keypoint arrays")
-        kl = np.ascontiguousarray(kl[:m])
-        kr = np.ascontiguousarray(kr[:m])
+        kl, kr, m = _keys(key_left, key_right, match_size)
         res, pol = capi.PairResult(), capi.PolishResult()
         mask = np.zeros(max(m, 1), np.uint8)
         st = self.ctx.L.erp_eight_point_find_polished(self.ctx.h, im_width, im_height, _np_ptr(kl),
                                                       _np_ptr(kr), m, C.byref(self.cfg), thr,
                                                       int(rounds), C.byref(res), C.byref(pol),
                                                       _np_ptr(mask))
-        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
-        self.last_polish = np.frombuffer(bytes(pol), POLISH_DTYPE)[0]
+        self.last_result = _record(res, RESULT_DTYPE)
+        self.last_polish = _record(pol, POLISH_DTYPE)
         check(st, "find_polished")
         return self.last_polish["R"].copy(), self.last_polish["T"].copy(), mask[:m].astype(bool)
 
@@ -287,13 +285,7 @@ class eight_point:  # noqa: N801  (reference class name)
         definite.  ``last_result`` is find's record, ``last_polish`` the polish's, ``last_pose``
         the pose record (POSE_DTYPE; its status is ERP_TOO_FEW_POINTS when no match could vote).
         Consumes a rand stream exactly as find does."""
-        kl = np.ascontiguousarray(key_left, np.float32).reshape(-1, 2)
-        kr = np.ascontiguousarray(key_right, np.float32).reshape(-1, 2)
-        m = kl.shape[0] if match_size is None else int(match_size)
-        if m > kl.shape[0] or m > kr.shape[0]:
-            raise ValueError("match_size larger than the keypoint arrays")
-        kl = np.ascontiguousarray(kl[:m])
-        kr = np.ascontiguousarray(kr[:m])
+        kl, kr, m = _keys(key_left, key_right, match_size)
         res, pol, pose = capi.PairResult(), capi.PolishResult(), capi.Pose()
         mask = np.zeros(max(m, 1), np.uint8)
         front = np.zeros(max(m, 1), np.uint8)
@@ -303,9 +295,9 @@ class eight_point:  # noqa: N801  (reference class name)
                                                    int(rounds), float(min_sin2), C.byref(res),
                                                    C.byref(pol), C.byref(pose), _np_ptr(mask),
                                                    _np_ptr(depth), _np_ptr(front))
-        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
-        self.last_polish = np.frombuffer(bytes(pol), POLISH_DTYPE)[0]
-        self.last_pose = np.frombuffer(bytes(pose), POSE_DTYPE)[0]
+        self.last_result = _record(res, RESULT_DTYPE)
+        self.last_polish = _record(pol, POLISH_DTYPE)
+        self.last_pose = _record(pose, POSE_DTYPE)
         check(st, "find_posed")
         return (self.last_pose["R"].copy(), self.last_pose["T"].copy(), mask[:m].astype(bool),
                 depth[:m], front[:m].astype(bool))
@@ -320,7 +312,7 @@ class eight_point:  # noqa: N801  (reference class name)
         res = capi.PairResult()
         st = self.ctx.L.erp_initial_guess(self.ctx.h, _np_ptr(bl), _np_ptr(br), m,
                                           C.byref(self.cfg), _np_ptr(R), _np_ptr(T), C.byref(res))
-        self.last_result = np.frombuffer(bytes(res), RESULT_DTYPE)[0]
+        self.last_result = _record(res, RESULT_DTYPE)
         check(st, "initial_guess")
         return R, T
 
@@ -333,7 +325,7 @@ class eight_point:  # noqa: N801  (reference class name)
         h = capi.Hypothesis()
         check(self.ctx.L.erp_eight_point_estimation(self.ctx.h, _np_ptr(bl), _np_ptr(br), m,
                                                     C.byref(h)), "eight_point_estimation")
-        r = np.frombuffer(bytes(h), HYP_DTYPE)[0]
+        r = _record(h, HYP_DTYPE)
         return (r["R1"].copy(), r["R2"].copy(), r["T"].copy(), bool(r["R1_valid"]),
                 bool(r["R2_valid"]), r["E"].copy())
 
@@ -941,6 +933,25 @@ class _PackedBuffers:
                 "band_counts": t["band_counts"][:n]}
 
 
+# where a record kind keeps its solved 9-vector and its status: (byte offset of E, of status)
+RECORD_SOURCES = {"winners": tuple(WINNER_DTYPE.fields[k][1] for k in ("E", "status")),
+                  "polish": tuple(POLISH_DTYPE.fields[k][1] for k in ("E", "status"))}
+
+
+def _record_source(where: str, source: str, out: dict, polish):
+    """-> (records, E offset, status offset) of select_pose's / guided_match's ``source=``: the
+    winner records of run()'s dict or the polish records of polish()'s"""
+    if source not in RECORD_SOURCES:
+        raise ValueError(f"{where}: source is 'winners' or 'polish'")
+    if source == "winners":
+        if "winners" not in out:
+            raise ValueError(f"{where}(source='winners') needs run(..., want=('winners',))")
+        return (out["winners"], *RECORD_SOURCES[source])
+    if polish is None or "polish" not in polish:
+        raise ValueError(f"{where}(source='polish') needs polish=polish(...)")
+    return (polish["polish"], *RECORD_SOURCES[source])
+
+
 class PairBatchRunner:
     """The fused hot path over a batch of ERP pairs held in device memory (torch tensors).
 
@@ -1149,14 +1160,10 @@ class PairBatchRunner:
         if missing:
             raise ValueError(f"select_pose needs run(..., want=('winners', 'key_left', "
                              f"'key_right')): missing {missing}")
-        if source == "winners":
-            src, e_off, s_off, mask = out["winners"], 16, 0, None
-        elif source == "polish":
-            if polish is None or "polish" not in polish or "mask" not in polish:
-                raise ValueError("select_pose(source='polish') needs polish=polish(...) with its mask")
-            src, e_off, s_off, mask = polish["polish"], 48, 24, polish["mask"]
-        else:
-            raise ValueError("select_pose: source is 'winners' or 'polish'")
+        if source == "polish" and (polish is None or "polish" not in polish or "mask" not in polish):
+            raise ValueError("select_pose(source='polish') needs polish=polish(...) with its mask")
+        src, e_off, s_off = _record_source("select_pose", source, out, polish)
+        mask = polish["mask"] if source == "polish" else None
         return self.ctx.select_pose(out["results"], out["key_left"], out["key_right"], width,
                                     height, src, e_off, s_off, mask=mask, thr=thr,
                                     min_sin2=min_sin2, want=want, stream=stream)
@@ -1181,16 +1188,7 @@ class PairBatchRunner:
             max_nt = int((off_r[1:] - off_r[:-1]).max().item()) if off_r.numel() > 1 else 0
         if "results" not in out:
             raise ValueError("guided_match needs run()'s dict with its results")
-        if source == "winners":
-            if "winners" not in out:
-                raise ValueError("guided_match(source='winners') needs run(..., want=('winners',))")
-            src, e_off, s_off = out["winners"], 16, 0
-        elif source == "polish":
-            if polish is None or "polish" not in polish:
-                raise ValueError("guided_match(source='polish') needs polish=polish(...)")
-            src, e_off, s_off = polish["polish"], 48, 24
-        else:
-            raise ValueError("guided_match: source is 'winners' or 'polish'")
+        src, e_off, s_off = _record_source("guided_match", source, out, polish)
         return self.ctx.guided_match(desc_l, desc_r, kp_l, kp_r, off_l, off_r, width, height,
                                      max_nq, max_nt, src, e_off, s_off, results=out["results"],
                                      thr=thr, ratio=ratio, max_dist=max_dist, unique=unique,

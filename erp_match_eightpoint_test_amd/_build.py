@@ -6,6 +6,7 @@ snapshot; nothing is installed into site-packages.
 """
 from __future__ import annotations
 
+import functools
 import os
 import subprocess
 import sys
@@ -24,7 +25,7 @@ SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
            "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp", "erp_ctx.hpp", "erp_winner.hpp",
-           "erp_l2.hpp"]
+           "erp_l2.hpp", "erp_block.hpp", "erp_stage.hpp", "erp_host_stage.hpp"]
 PUBLIC_HEADERS = ["erp_match.h", os.path.join("erp", "feature_matcher.hpp"),
                   os.path.join("erp", "eight_point.hpp"), os.path.join("erp", "rand_stream.hpp")]
 
@@ -109,26 +110,25 @@ def build(force: bool = False, verbose: bool = False, lib_path: str = LIB_PATH,
     return lib_path
 
 
-DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "class_api_driver.cpp")
-DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "class_api_driver")
-# two successive erp::eight_point objects on erp::rand_stream::process()
-STREAM_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "rand_stream_driver.cpp")
-STREAM_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "rand_stream_driver")
-# erp::eight_point::find_polished
-POLISH_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "polish_driver.cpp")
-POLISH_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "polish_driver")
-# erp::eight_point::find_winner
-WINNER_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "winner_driver.cpp")
-WINNER_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "winner_driver")
-# erp::eight_point::find_posed
-POSE_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "pose_driver.cpp")
-POSE_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "pose_driver")
-# erp::feature_matcher::match_guided
-GUIDED_DRIVER_SRC = os.path.join(ROOT, "tests", "cpp", "guided_driver.cpp")
-GUIDED_DRIVER_BIN = os.path.join(ROOT, "tests", "cpp", "guided_driver")
+# the C++ class-API drivers (tests/cpp/<file>.cpp -> tests/cpp/<file>), by name
+DRIVERS = {
+    "class_api": "class_api_driver",
+    "stream": "rand_stream_driver",  # two successive erp::eight_point objects on erp::rand_stream::process()
+    "polish": "polish_driver",       # erp::eight_point::find_polished
+    "winner": "winner_driver",       # erp::eight_point::find_winner
+    "pose": "pose_driver",           # erp::eight_point::find_posed
+    "guided": "guided_driver",       # erp::feature_matcher::match_guided
+}
 
 
-def _build_cpp_driver(src: str, out: str, force: bool) -> str:
+def build_driver(name: str | None = None, force: bool = False) -> str:
+    """A C++ class-API driver of DRIVERS: host code only, g++ against liberp_match.so -- the
+    link a reference maintainer would do.  name=None builds all of
+    them and returns the class API driver."""
+    if name is None:
+        return [build_driver(n, force) for n in DRIVERS][0]
+    out = os.path.join(ROOT, "tests", "cpp", DRIVERS[name])
+    src = out + ".cpp"
     if (not force and os.path.exists(out)
             and os.path.getmtime(out) >= max(os.path.getmtime(src), os.path.getmtime(LIB_PATH))):
         return out
@@ -139,38 +139,10 @@ def _build_cpp_driver(src: str, out: str, force: bool) -> str:
     return out
 
 
-def build_driver(force: bool = False) -> str:
-    """the C++ class-API drivers (tests/cpp): host code only, g++ against liberp_match.so -- the
-    link a reference maintainer would do.  Returns the class API
-    driver; build_stream_driver() the rand stream one, build_polish_driver() the polish one,
-    build_winner_driver() the winner one, build_pose_driver() the pose one,
-    build_guided_driver() the guided matching one."""
-    _build_cpp_driver(STREAM_DRIVER_SRC, STREAM_DRIVER_BIN, force)
-    _build_cpp_driver(POLISH_DRIVER_SRC, POLISH_DRIVER_BIN, force)
-    _build_cpp_driver(WINNER_DRIVER_SRC, WINNER_DRIVER_BIN, force)
-    _build_cpp_driver(POSE_DRIVER_SRC, POSE_DRIVER_BIN, force)
-    _build_cpp_driver(GUIDED_DRIVER_SRC, GUIDED_DRIVER_BIN, force)
-    return _build_cpp_driver(DRIVER_SRC, DRIVER_BIN, force)
-
-
-def build_stream_driver(force: bool = False) -> str:
-    return _build_cpp_driver(STREAM_DRIVER_SRC, STREAM_DRIVER_BIN, force)
-
-
-def build_polish_driver(force: bool = False) -> str:
-    return _build_cpp_driver(POLISH_DRIVER_SRC, POLISH_DRIVER_BIN, force)
-
-
-def build_winner_driver(force: bool = False) -> str:
-    return _build_cpp_driver(WINNER_DRIVER_SRC, WINNER_DRIVER_BIN, force)
-
-
-def build_pose_driver(force: bool = False) -> str:
-    return _build_cpp_driver(POSE_DRIVER_SRC, POSE_DRIVER_BIN, force)
-
-
-def build_guided_driver(force: bool = False) -> str:
-    return _build_cpp_driver(GUIDED_DRIVER_SRC, GUIDED_DRIVER_BIN, force)
+# build_stream_driver(force=False), build_polish_driver, ...: each driver's own name, from the table
+for _name in DRIVERS:
+    if _name != "class_api":
+        globals()[f"build_{_name}_driver"] = functools.partial(build_driver, _name)
 
 
 if __name__ == "__main__":

@@ -452,6 +452,28 @@ def process_rand_stream(device: int = 0) -> RandStream:
     return RandStream(_handle=h)
 
 
+def _check_tensors(where: str, pairs):
+    """every (tensor, dtype) of pairs is a contiguous CUDA tensor of that dtype"""
+    import torch
+    for t, dt in pairs:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
+                not t.is_contiguous():
+            raise ValueError(f"{where}: inputs must be contiguous CUDA tensors of the C types")
+
+
+def _stream_or_current(stream, dev):
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+
+
+def _alloc_outputs(shapes: dict, names, dev):
+    """-> (out, ptr): the outputs ``names`` of shapes = {name: (shape, dtype)} as fresh tensors,
+    and ptr(name) = its device address, None for an output that was not asked for"""
+    import torch
+    out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in names}
+    return out, lambda k: out[k].data_ptr() if k in out else None
+
+
 class Context:
     """erp_ctx: one per device/thread; owns the grow-only device scratch."""
 
@@ -503,11 +525,9 @@ class Context:
         import torch
         from_winners = hyps is None
         rec = winners if from_winners else hyps
-        for t, dt in ((results, torch.uint8), (rec, torch.uint8), (key_left, torch.float32),
-                      (key_right, torch.float32), (width, torch.int32), (height, torch.int32)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
-                    not t.is_contiguous():
-                raise ValueError("polish: inputs must be contiguous CUDA tensors of the C types")
+        _check_tensors("polish", ((results, torch.uint8), (rec, torch.uint8),
+                                  (key_left, torch.float32), (key_right, torch.float32),
+                                  (width, torch.int32), (height, torch.int32)))
         n = results.shape[0]
         rec_ok = (rec.dim() == 2 and rec.shape[1] == WINNER_DTYPE.itemsize) if from_winners else \
             (rec.dim() == 3 and rec.shape[2] == HYP_DTYPE.itemsize)
@@ -524,16 +544,13 @@ class Context:
                            key_left.data_ptr(), key_right.data_ptr(), width.data_ptr(),
                            height.data_ptr(), results.data_ptr(),
                            None if from_winners else hyps.data_ptr())
-        out = {"polish": torch.empty((n, POLISH_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
-        if want_rounds:
-            out["rounds"] = torch.empty((n, max(rounds, 0), POLISH_ROUND_DTYPE.itemsize),
-                                        dtype=torch.uint8, device=dev)
-        if want_mask:
-            out["mask"] = torch.empty((n, key_left.shape[1]), dtype=torch.uint8, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        tail = (valid_abs, thr, rounds, out["polish"].data_ptr(),
-                out["rounds"].data_ptr() if want_rounds and rounds > 0 else None,
-                out["mask"].data_ptr() if want_mask else None, st)
+        shapes = {"polish": ((n, POLISH_DTYPE.itemsize), torch.uint8),
+                  "rounds": ((n, max(rounds, 0), POLISH_ROUND_DTYPE.itemsize), torch.uint8),
+                  "mask": ((n, key_left.shape[1]), torch.uint8)}
+        names = ["polish"] + ["rounds"] * bool(want_rounds) + ["mask"] * bool(want_mask)
+        out, ptr = _alloc_outputs(shapes, names, dev)
+        tail = (valid_abs, thr, rounds, ptr("polish"), ptr("rounds") if rounds > 0 else None,
+                ptr("mask"), _stream_or_current(stream, dev))
         if from_winners:
             check(self.L.erp_polish_winners_dev(self.h, C.byref(inp), winners.data_ptr(), *tail),
                   "erp_polish_winners_dev")
@@ -557,11 +574,7 @@ class Context:
                (key_right, torch.float32), (width, torch.int32), (height, torch.int32)]
         if mask is not None:
             chk.append((mask, torch.uint8))
-        for t, dt in chk:
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
-                    not t.is_contiguous():
-                raise ValueError("select_pose: inputs must be contiguous CUDA tensors of the C "
-                                 "types")
+        _check_tensors("select_pose", chk)
         n = results.shape[0]
         if results.dim() != 2 or results.shape[1] != RESULT_DTYPE.itemsize or source.dim() != 2 or \
                 source.shape[0] != n or e_offset < 0 or e_offset + 72 > source.shape[1] or \
@@ -582,17 +595,13 @@ class Context:
                          source.data_ptr() + e_offset, rec,
                          None if status_offset is None else source.data_ptr() + status_offset,
                          rec, None if mask is None else mask.data_ptr())
-        out = {"pose": torch.empty((n, POSE_DTYPE.itemsize), dtype=torch.uint8, device=dev)}
-        if "depth" in want:
-            out["depth"] = torch.empty((n, stride, 2), dtype=torch.float64, device=dev)
-        if "front" in want:
-            out["front"] = torch.empty((n, stride), dtype=torch.uint8, device=dev)
-        if "results" in want:
-            out["results"] = torch.empty((n, RESULT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
+        shapes = {"pose": ((n, POSE_DTYPE.itemsize), torch.uint8),
+                  "depth": ((n, stride, 2), torch.float64), "front": ((n, stride), torch.uint8),
+                  "results": ((n, RESULT_DTYPE.itemsize), torch.uint8)}
+        out, ptr = _alloc_outputs(shapes, ["pose", *want], dev)
         check(self.L.erp_pose_select_dev(self.h, C.byref(inp), thr, min_sin2, ptr("pose"),
-                                         ptr("depth"), ptr("front"), ptr("results"), st),
+                                         ptr("depth"), ptr("front"), ptr("results"),
+                                         _stream_or_current(stream, dev)),
               "erp_pose_select_dev")
         return out
 
@@ -616,11 +625,7 @@ class Context:
                (width, torch.int32), (height, torch.int32), (source, torch.uint8)]
         if results is not None:
             chk.append((results, torch.uint8))
-        for t, dt in chk:
-            if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda or \
-                    not t.is_contiguous():
-                raise ValueError("guided_match: inputs must be contiguous CUDA tensors of the C "
-                                 "types")
+        _check_tensors("guided_match", chk)
         n = off_l.shape[0] - 1
         if off_r.shape[0] != n + 1 or width.numel() != n or height.numel() != n or \
                 source.dim() != 2 or source.shape[0] != n or e_offset < 0 or \
@@ -640,20 +645,17 @@ class Context:
                       width.data_ptr(), height.data_ptr()),
             None if results is None else results.data_ptr(), source.data_ptr() + e_offset, rec,
             None if status_offset is None else source.data_ptr() + status_offset, rec)
-        shapes = {"matches": ((n, max_nq, 4), torch.int32),
+        shapes = {"count": ((n,), torch.int32), "matches": ((n, max_nq, 4), torch.int32),
                   "key_left": ((n, max_nq, 2), torch.float32),
                   "key_right": ((n, max_nq, 2), torch.float32), "gated": ((n,), torch.int64),
                   "results": ((n, RESULT_DTYPE.itemsize), torch.uint8),
                   "winners": ((n, WINNER_DTYPE.itemsize), torch.uint8)}
-        out = {"count": torch.empty((n,), dtype=torch.int32, device=dev)}
-        for k in want:
-            out[k] = torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev)
-        ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
+        out, ptr = _alloc_outputs(shapes, ["count", *want], dev)
         o = GuidedOutputs(ptr("count"), ptr("matches"), ptr("key_left"), ptr("key_right"),
                           ptr("gated"), ptr("results"), ptr("winners"))
         cfg = GuidedCfg(thr, ratio, max_dist, 1 if unique else 0)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        check(self.L.erp_match_guided_dev(self.h, C.byref(inp), C.byref(cfg), C.byref(o), st),
+        check(self.L.erp_match_guided_dev(self.h, C.byref(inp), C.byref(cfg), C.byref(o),
+                                          _stream_or_current(stream, dev)),
               "erp_match_guided_dev")
         return out
 

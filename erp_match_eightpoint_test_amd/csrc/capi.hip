@@ -1175,17 +1175,12 @@ static erp_status find_host(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2
     // one lock across upload, find and download: the staging buffers are the context's
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     ERP_CK(hipSetDevice(ctx->device));
-    if (!ensure(ctx->in_a, (size_t)m * 8 + 8) || !ensure(ctx->in_b, (size_t)m * 8 + 8) ||
-        !ensure(ctx->in_c, sizeof(erp_pair_result) + sizeof(erp_winner)))
-        return ERP_OUT_OF_MEMORY;
-    if (m > 0) {
-        ERP_CK(hipMemcpy(ctx->in_a.p, h_kl, (size_t)m * 8, hipMemcpyHostToDevice));
-        ERP_CK(hipMemcpy(ctx->in_b.p, h_kr, (size_t)m * 8, hipMemcpyHostToDevice));
-    }
+    if (!ensure(ctx->in_c, sizeof(erp_pair_result) + sizeof(erp_winner))) return ERP_OUT_OF_MEMORY;
+    erp_status s = erp::upload_keys(ctx, h_kl, h_kr, m);
+    if (s != ERP_OK) return s;
     erp_winner* d_winner = h_winner ? (erp_winner*)((erp_pair_result*)ctx->in_c.p + 1) : nullptr;
-    erp_status s = find_dev(ctx, W, H, (const erp_point2f*)ctx->in_a.p,
-                            (const erp_point2f*)ctx->in_b.p, m, cfg,
-                            (erp_pair_result*)ctx->in_c.p, nullptr, d_winner, nullptr);
+    s = find_dev(ctx, W, H, erp::keys_left(ctx), erp::keys_right(ctx), m, cfg,
+                 (erp_pair_result*)ctx->in_c.p, nullptr, d_winner, nullptr);
     if (s != ERP_OK) return s;
     erp_pair_result r;
     ERP_CK(hipMemcpy(&r, ctx->in_c.p, sizeof(r), hipMemcpyDeviceToHost));

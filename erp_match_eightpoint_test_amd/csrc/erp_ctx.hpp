@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/erp_match.h"
+#include "erp_host_stage.hpp"
 
 #define ERP_CK(x)                                         \
     do {                                                  \
@@ -44,15 +45,13 @@ enum CtxSlot {
     // sweep.hip: the group's rotated images, the left image's keypoints / descriptors / counts,
     // the matched keypoints of erp_image_sweep_run's match error
     kSlotSweepCanvas, kSlotLeftKp, kSlotLeftDesc, kSlotLeftCount, kSlotSweepKeyL, kSlotSweepKeyR,
-    // polish.hip: the device side of erp_eight_point_find_polished (hypothesis records, polish
-    // record, W / H, mask)
-    kSlotPolishHost,
-    // pose.hip: the device side of erp_eight_point_find_posed (result, winner, polish and pose
-    // records, W / H, depths, mask, front)
-    kSlotPoseHost,
+    // the device side of erp_eight_point_find_polished, erp_eight_point_find_posed and
+    // erp_match_guided, laid out by erp_host_stage.hpp: each call holds the context lock from
+    // its upload to its blocking download, so the three never use the slot at the same time
+    kSlotHostStage,
     // guided.hip: the per-query (j0, e0, e1, |G_i|) records, the per-train-row 64-bit claim
-    // words, the train bearings with each pair's E', and the device side of erp_match_guided
-    kSlotGuidedQuery, kSlotGuidedClaim, kSlotGuidedBearings, kSlotGuidedHost,
+    // words, and the train bearings with each pair's E'
+    kSlotGuidedQuery, kSlotGuidedClaim, kSlotGuidedBearings,
     kCtxSlotCount
 };
 
@@ -167,6 +166,35 @@ T* ctx_scratch(erp_ctx* ctx, CtxSlot slot, size_t bytes) {
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     DevBuf& b = ctx->extra[slot];
     return ensure(b, bytes) ? (T*)b.p : nullptr;
+}
+
+// A one-pair host call's keypoints into in_a / in_b (blocking copies, under the context lock).
+inline erp_status upload_keys(erp_ctx* ctx, const erp_point2f* h_kl, const erp_point2f* h_kr,
+                              int32_t m) {
+    if (!ensure(ctx->in_a, (size_t)m * 8 + 8) || !ensure(ctx->in_b, (size_t)m * 8 + 8))
+        return ERP_OUT_OF_MEMORY;
+    if (m > 0) {
+        ERP_CK(hipMemcpy(ctx->in_a.p, h_kl, (size_t)m * 8, hipMemcpyHostToDevice));
+        ERP_CK(hipMemcpy(ctx->in_b.p, h_kr, (size_t)m * 8, hipMemcpyHostToDevice));
+    }
+    return ERP_OK;
+}
+inline const erp_point2f* keys_left(const erp_ctx* ctx) { return (const erp_point2f*)ctx->in_a.p; }
+inline const erp_point2f* keys_right(const erp_ctx* ctx) { return (const erp_point2f*)ctx->in_b.p; }
+
+// the stage inputs of such a call (erp_polish_inputs, erp_pose_inputs: the same leading fields)
+// over the uploaded keypoints; d_wh = {W, H} on the device
+template <class In>
+In one_pair_inputs(const erp_ctx* ctx, int32_t m, const int32_t* d_wh, const erp_pair_result* d_res) {
+    In in{};
+    in.n_pairs = 1;
+    in.key_stride = m;
+    in.key_left = keys_left(ctx);
+    in.key_right = keys_right(ctx);
+    in.width = d_wh;
+    in.height = d_wh + 1;
+    in.results = d_res;
+    return in;
 }
 
 // records an event pair around one launch when profiling is on

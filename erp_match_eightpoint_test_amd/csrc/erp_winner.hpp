@@ -8,21 +8,12 @@
 #include <stdint.h>
 
 #include "../../include/erp_match.h"
+#include "erp_block.hpp"
 
 namespace erp {
 
 constexpr int kWinnerThreads = 256;
 constexpr int kWinnerWaves = kWinnerThreads / 64;
-
-// inclusive prefix sum over the wave's 64 lanes
-__device__ __forceinline__ int winner_wave_scan(int x, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x;
-}
 
 // From the hypothesis records' two validity flags: a block prefix scan over 256-record chunks
 // (the strided read of the 120-B records stops at the chunk that holds the winner).  Every
@@ -30,7 +21,7 @@ __device__ __forceinline__ int winner_wave_scan(int x, int lane) {
 // no row of these records), win[1] = 0 for its R1, 1 for its R2; ends past a barrier.
 __device__ inline void winner_from_records(const erp_hypothesis* hyps, int iters, int min_idx,
                                            int* wsum, int* win) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) win[0] = -1;
     __syncthreads();
     int base = 0;
@@ -41,16 +32,9 @@ __device__ inline void winner_from_records(const erp_hypothesis* hyps, int iters
             v1 = hyps[h].R1_valid != 0;
             c = v1 + (hyps[h].R2_valid != 0);
         }
-        const int x = winner_wave_scan(c, lane);
-        if (lane == 63) wsum[wave] = x;
-        __syncthreads();
-        int wbase = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < kWinnerWaves; w++) {
-            wbase += w < wave ? wsum[w] : 0;
-            total += wsum[w];
-        }
-        const int first = base + wbase + x - c;  // the row this record's first rotation got
+        int total;
+        // the row this record's first rotation got
+        const int first = base + block_exclusive_scan<kWinnerThreads>(c, wsum, &total);
         if (c && min_idx >= first && min_idx < first + c) {
             win[0] = h;
             win[1] = (v1 && min_idx == first) ? 0 : 1;

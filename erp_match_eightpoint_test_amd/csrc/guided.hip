@@ -37,10 +37,12 @@
 #include <type_traits>
 
 #include "../../include/erp_match.h"
+#include "erp_block.hpp"
 #include "erp_ctx.hpp"
 #include "erp_device.hpp"
 #include "erp_l2.hpp"
 #include "erp_launch.hpp"
+#include "erp_stage.hpp"
 
 // development variants (the _build.build(defines=...) route; DESIGN.md 3.18 has both timings)
 #ifndef ERP_GUIDED_COMPACT
@@ -64,7 +66,6 @@ constexpr int kTile = 64;          // train rows per LDS tile: one bit of the pa
 constexpr int kRowStride = 68;     // floats per staged row: 16-lane b128 groups on distinct banks
 constexpr int kItemList = 256;     // gated (query, row) items per wave and tile (more: per-lane loop)
 constexpr int kCompactThreads = 1024;
-constexpr int kMaxNq = 65535;      // as erp_pair_batch_run
 constexpr int kXcds = 8;
 
 // one query's outcome of the gate kernel
@@ -89,43 +90,10 @@ struct GuidedArgs {
     unsigned long long* claim;     // [n_pairs][max_nt]
 };
 
-// exclusive scan over a block of BLOCK threads (the matcher's merge uses the same one)
-template <int BLOCK>
-__device__ int block_exclusive_scan(int v, int* ws, int* total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) ws[wid] = x;
-    __syncthreads();
-    if (wid == 0) {
-        int t = lane < BLOCK / 64 ? ws[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < BLOCK / 64; o <<= 1) {
-            const int y = __shfl_up(t, o, 64);
-            if (lane >= o) t += y;
-        }
-        if (lane < BLOCK / 64) ws[lane] = t;
-    }
-    __syncthreads();
-    const int base = wid ? ws[wid - 1] : 0;
-    *total = ws[BLOCK / 64 - 1];
-    __syncthreads();
-    return base + x - v;
-}
-
-// rule 7: the result's status first, then the source's (block-uniform)
+// rule 7: the result's status first, then the source's (no match count: the batch bounds the rows)
 __device__ __forceinline__ int32_t pair_status(const GuidedArgs& a, int p) {
-    if (a.in.results) {
-        const int32_t s = a.in.results[p].status;
-        if (s != ERP_OK) return s;
-    }
-    if (a.in.src_status)
-        return *(const int32_t*)((const char*)a.in.src_status + (size_t)p * a.in.src_status_stride);
-    return ERP_OK;
+    return stage_gate(a.in.results ? a.in.results[p].status : (int32_t)ERP_OK, 0,
+                      source_of(a.in).status_of(p));
 }
 
 // the pair's row counts, never above the bounds the scratch was sized for
@@ -151,7 +119,7 @@ __global__ __launch_bounds__(256) void guided_prep_kernel(GuidedArgs a) {
     if (j == 0) {
         if (a.out.gated) a.out.gated[p] = 0;
         if (pair_status(a, p) == ERP_OK) {
-            const double* e = (const double*)((const char*)a.in.e + (size_t)p * a.in.e_stride);
+            const double* e = source_of(a.in).e_of(p);
             double e9[9], Ec[9];
 #pragma unroll
             for (int k = 0; k < 9; k++) e9[k] = e[k];
@@ -319,12 +287,7 @@ __global__ __launch_bounds__(kGateThreads) ERP_GUIDED_GATE_WAVES void guided_gat
         bool listed = false;
         int first = 0, total = 0;
         if constexpr (kCompact) {
-            int x = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int y = __shfl_up(x, o, 64);
-                if (lane >= o) x += y;
-            }
+            const int x = wave_inclusive_scan(mine, lane);
             total = __shfl(x, 63, 64);
             first = x - mine;
             listed = total <= kItemList;  // (wave-uniform)
@@ -381,8 +344,6 @@ __global__ __launch_bounds__(kGateThreads) ERP_GUIDED_GATE_WAVES void guided_gat
                   ((unsigned long long)__float_as_uint(d0) << 32) | (unsigned)i);
 }
 
-static_assert(sizeof(erp_pair_result) == 64 && offsetof(erp_pair_result, M) == 28,
-              "guided_compact_kernel patches M in word 3");
 static_assert(sizeof(erp_winner) == 88, "guided_compact_kernel writes 11 words");
 
 __global__ __launch_bounds__(kCompactThreads) void guided_compact_kernel(GuidedArgs a) {
@@ -430,23 +391,15 @@ __global__ __launch_bounds__(kCompactThreads) void guided_compact_kernel(GuidedA
     __syncthreads();  // every read of the result record is done (results_out may be the input)
     if (tid != 0) return;
     a.out.count[p] = base;
-    if (a.out.results_out) {  // every byte copied (as eight 64-bit words), M replaced
-        const uint64_t* src = (const uint64_t*)(a.in.results + p);
-        uint64_t* dst = (uint64_t*)(a.out.results_out + p);
-        uint64_t w[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) w[k] = src[k];
-        w[3] = (w[3] & 0xffffffffull) | ((uint64_t)(uint32_t)base << 32);
-#pragma unroll
-        for (int k = 0; k < 8; k++) dst[k] = w[k];
-    }
+    if (a.out.results_out)  // M replaced
+        copy_result(a.out.results_out + p, a.in.results + p, [=](uint64_t* w) {
+            w[3] = (w[3] & 0xffffffffull) | ((uint64_t)(uint32_t)base << 32);
+        });
     if (a.out.winners_out) {
-        erp_winner o;
-        memset(&o, 0, sizeof(o));
-        o.status = status;
+        erp_winner o = stage_record<erp_winner>(status);
         if (status == ERP_OK) {
             o.iter = -1;
-            const double* e = (const double*)((const char*)a.in.e + (size_t)p * a.in.e_stride);
+            const double* e = source_of(a.in).e_of(p);
 #pragma unroll
             for (int k = 0; k < 9; k++) o.E[k] = e[k];
         }
@@ -464,15 +417,11 @@ erp_status erp_match_guided_dev(erp_ctx* ctx, const erp_guided_inputs* in,
     if (!ctx || !in || !cfg || !out || !out->count || in->batch.n_pairs < 0) return ERP_INVALID_ARG;
     const erp_pair_batch& b = in->batch;
     if (!(cfg->thr > 0) || !(cfg->ratio > 0) || std::isnan(cfg->max_dist) || b.dim != kDim ||
-        b.max_nq < 0 || b.max_nt < 0 || b.max_nq > kMaxNq)
+        b.max_nq < 0 || b.max_nt < 0 || b.max_nq > kStageMaxM)
         return ERP_INVALID_ARG;
     if (b.n_pairs == 0) return ERP_OK;
     if (!b.desc_l || !b.desc_r || !b.kp_l || !b.kp_r || !b.off_l || !b.off_r || !b.width ||
-        !b.height || !in->e || in->e_stride < 0 || (in->e_stride & 7) != 0 ||
-        ((uintptr_t)in->e & 7) != 0 ||
-        (in->src_status && (in->src_status_stride < 0 || (in->src_status_stride & 3) != 0 ||
-                            ((uintptr_t)in->src_status & 3) != 0)) ||
-        (!in->results && out->results_out))
+        !b.height || !source_ok(source_of(*in)) || (!in->results && out->results_out))
         return ERP_INVALID_ARG;
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
@@ -511,51 +460,47 @@ erp_status erp_match_guided(erp_ctx* ctx, const float* h_desc1, int32_t n1, cons
                             int32_t n2, const erp_point2f* h_kp1, const erp_point2f* h_kp2,
                             int32_t W, int32_t H, const double E[9], const erp_guided_cfg* cfg,
                             erp_dmatch* h_out, int32_t* h_count) {
-    if (!ctx || !cfg || !E || !h_count || n1 < 0 || n2 < 0 || n1 > kMaxNq || W <= 0 || H <= 0 ||
+    if (!ctx || !cfg || !E || !h_count || n1 < 0 || n2 < 0 || n1 > kStageMaxM || W <= 0 || H <= 0 ||
         (n1 > 0 && (!h_desc1 || !h_kp1 || !h_out)) || (n2 > 0 && (!h_desc2 || !h_kp2)))
         return ERP_INVALID_ARG;
     *h_count = 0;
     // one lock across upload, match and download: the staging buffer is the context's
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     ERP_CK(hipSetDevice(ctx->device));
-    // the device side: E, the offsets, the descriptors (16-byte aligned: 112), the matches, the
-    // keypoints, W / H and the count
-    const size_t o_off = 80, o_d1 = o_off + 32, o_d2 = o_d1 + (size_t)n1 * kDim * 4,
-                 o_out = o_d2 + (size_t)n2 * kDim * 4, o_k1 = o_out + (size_t)n1 * sizeof(erp_dmatch),
-                 o_k2 = o_k1 + (size_t)n1 * 8, o_wh = o_k2 + (size_t)n2 * 8, o_cnt = o_wh + 8;
-    char* base = erp::ctx_scratch<char>(ctx, erp::kSlotGuidedHost, o_cnt + 8);
+    const GuidedStage L(n1, n2);
+    char* base = ctx_scratch<char>(ctx, kSlotHostStage, L.bytes);
     if (!base) return ERP_OUT_OF_MEMORY;
     const int64_t off[4] = {0, n1, 0, n2};
     const int32_t wh[2] = {W, H};
-    ERP_CK(hipMemcpy(base, E, 72, hipMemcpyHostToDevice));
-    ERP_CK(hipMemcpy(base + o_off, off, sizeof(off), hipMemcpyHostToDevice));
-    ERP_CK(hipMemcpy(base + o_wh, wh, sizeof(wh), hipMemcpyHostToDevice));
+    ERP_CK(hipMemcpy(base + L.e, E, 72, hipMemcpyHostToDevice));
+    ERP_CK(hipMemcpy(base + L.off, off, sizeof(off), hipMemcpyHostToDevice));
+    ERP_CK(hipMemcpy(base + L.wh, wh, sizeof(wh), hipMemcpyHostToDevice));
     if (n1 > 0) {
-        ERP_CK(hipMemcpy(base + o_d1, h_desc1, (size_t)n1 * kDim * 4, hipMemcpyHostToDevice));
-        ERP_CK(hipMemcpy(base + o_k1, h_kp1, (size_t)n1 * 8, hipMemcpyHostToDevice));
+        ERP_CK(hipMemcpy(base + L.desc1, h_desc1, (size_t)n1 * kDim * 4, hipMemcpyHostToDevice));
+        ERP_CK(hipMemcpy(base + L.kp1, h_kp1, (size_t)n1 * 8, hipMemcpyHostToDevice));
     }
     if (n2 > 0) {
-        ERP_CK(hipMemcpy(base + o_d2, h_desc2, (size_t)n2 * kDim * 4, hipMemcpyHostToDevice));
-        ERP_CK(hipMemcpy(base + o_k2, h_kp2, (size_t)n2 * 8, hipMemcpyHostToDevice));
+        ERP_CK(hipMemcpy(base + L.desc2, h_desc2, (size_t)n2 * kDim * 4, hipMemcpyHostToDevice));
+        ERP_CK(hipMemcpy(base + L.kp2, h_kp2, (size_t)n2 * 8, hipMemcpyHostToDevice));
     }
     erp_guided_inputs in{};
     in.batch.n_pairs = 1;
     in.batch.dim = kDim;
     in.batch.max_nq = n1;
     in.batch.max_nt = n2;
-    in.batch.desc_l = (const float*)(base + o_d1);
-    in.batch.desc_r = (const float*)(base + o_d2);
-    in.batch.kp_l = (const erp_point2f*)(base + o_k1);
-    in.batch.kp_r = (const erp_point2f*)(base + o_k2);
-    in.batch.off_l = (const int64_t*)(base + o_off);
+    in.batch.desc_l = (const float*)(base + L.desc1);
+    in.batch.desc_r = (const float*)(base + L.desc2);
+    in.batch.kp_l = (const erp_point2f*)(base + L.kp1);
+    in.batch.kp_r = (const erp_point2f*)(base + L.kp2);
+    in.batch.off_l = (const int64_t*)(base + L.off);
     in.batch.off_r = in.batch.off_l + 2;
-    in.batch.width = (const int32_t*)(base + o_wh);
+    in.batch.width = (const int32_t*)(base + L.wh);
     in.batch.height = in.batch.width + 1;
-    in.e = base;
+    in.e = base + L.e;
     in.e_stride = 72;
     erp_guided_outputs out{};
-    out.count = (int32_t*)(base + o_cnt);
-    out.matches = (erp_dmatch*)(base + o_out);
+    out.count = (int32_t*)(base + L.count);
+    out.matches = (erp_dmatch*)(base + L.matches);
     const erp_status s = erp_match_guided_dev(ctx, &in, cfg, &out, nullptr);
     if (s != ERP_OK) return s;
     ERP_CK(hipDeviceSynchronize());

@@ -95,28 +95,31 @@ void eight_point::use_stream(rand_stream* s) {
     check(erp_ctx_set_rand_stream(ctx_, s ? s->handle() : nullptr), "use_stream");
 }
 
-void eight_point::find(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
-                       Vec3f& R, Vec3f& T, int match_size) {
+// the first match_size keypoints of each side as the C ABI takes them; `where` names the check
+static void keys(const std::vector<KeyPoint>& kl, const std::vector<KeyPoint>& kr, int match_size,
+                 const char* where, std::vector<erp_point2f>& a, std::vector<erp_point2f>& b) {
     if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
-        throw error(ERP_INVALID_ARG, "find: match_size");
-    std::vector<erp_point2f> a((size_t)match_size), b((size_t)match_size);
+        throw error(ERP_INVALID_ARG, where);
+    a.resize((size_t)match_size);
+    b.resize((size_t)match_size);
     for (int i = 0; i < match_size; i++) {
         a[i] = erp_point2f{kl[i].pt.x, kl[i].pt.y};
         b[i] = erp_point2f{kr[i].pt.x, kr[i].pt.y};
     }
+}
+
+void eight_point::find(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
+                       Vec3f& R, Vec3f& T, int match_size) {
+    std::vector<erp_point2f> a, b;
+    keys(kl, kr, match_size, "find: match_size", a, b);
     check(erp_eight_point_find(ctx_, W, H, a.data(), b.data(), match_size, &cfg, R.val, T.val, &last_),
           "find");
 }
 
 void eight_point::find_winner(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
                               Vec3f& R, Vec3f& T, int match_size, erp_winner& winner) {
-    if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
-        throw error(ERP_INVALID_ARG, "find_winner: match_size");
-    std::vector<erp_point2f> a((size_t)match_size), b((size_t)match_size);
-    for (int i = 0; i < match_size; i++) {
-        a[i] = erp_point2f{kl[i].pt.x, kl[i].pt.y};
-        b[i] = erp_point2f{kr[i].pt.x, kr[i].pt.y};
-    }
+    std::vector<erp_point2f> a, b;
+    keys(kl, kr, match_size, "find_winner: match_size", a, b);
     check(erp_eight_point_find_winner(ctx_, W, H, a.data(), b.data(), match_size, &cfg, R.val,
                                       T.val, &last_, &winner),
           "find_winner");
@@ -126,13 +129,8 @@ void eight_point::find_winner(int W, int H, std::vector<KeyPoint>& kl, std::vect
 void eight_point::find_polished(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
                                 Vec3f& R, Vec3f& T, int match_size, float thr, int rounds,
                                 std::vector<uint8_t>* inlier_mask) {
-    if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
-        throw error(ERP_INVALID_ARG, "find_polished: match_size");
-    std::vector<erp_point2f> a((size_t)match_size), b((size_t)match_size);
-    for (int i = 0; i < match_size; i++) {
-        a[i] = erp_point2f{kl[i].pt.x, kl[i].pt.y};
-        b[i] = erp_point2f{kr[i].pt.x, kr[i].pt.y};
-    }
+    std::vector<erp_point2f> a, b;
+    keys(kl, kr, match_size, "find_polished: match_size", a, b);
     if (inlier_mask) inlier_mask->assign((size_t)match_size, 0);
     check(erp_eight_point_find_polished(ctx_, W, H, a.data(), b.data(), match_size, &cfg, thr,
                                         rounds, &last_, &last_polish_,
@@ -148,13 +146,8 @@ void eight_point::find_posed(int W, int H, std::vector<KeyPoint>& kl, std::vecto
                              Vec3f& R, Vec3f& T, int match_size, float thr, int rounds,
                              double min_sin2, std::vector<uint8_t>* inlier_mask,
                              std::vector<double>* depth, std::vector<uint8_t>* front) {
-    if (match_size < 0 || (size_t)match_size > kl.size() || (size_t)match_size > kr.size())
-        throw error(ERP_INVALID_ARG, "find_posed: match_size");
-    std::vector<erp_point2f> a((size_t)match_size), b((size_t)match_size);
-    for (int i = 0; i < match_size; i++) {
-        a[i] = erp_point2f{kl[i].pt.x, kl[i].pt.y};
-        b[i] = erp_point2f{kr[i].pt.x, kr[i].pt.y};
-    }
+    std::vector<erp_point2f> a, b;
+    keys(kl, kr, match_size, "find_posed: match_size", a, b);
     if (inlier_mask) inlier_mask->assign((size_t)match_size, 0);
     if (depth) depth->assign((size_t)match_size * 2, 0.0);
     if (front) front->assign((size_t)match_size, 0);

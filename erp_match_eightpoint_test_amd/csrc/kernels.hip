@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "erp_block.hpp"
 #include "erp_device.hpp"
 #include "erp_jump_poly.hpp"
 #include "erp_kernels.hpp"
@@ -45,34 +46,6 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 __constant__ uint32_t c_red[30][31];
 
 __device__ __forceinline__ int wave_lane() { return threadIdx.x & 63; }
-
-// exclusive scan over a block of BLOCK threads (BLOCK multiple of 64, <= 1024)
-template <int BLOCK>
-__device__ int block_exclusive_scan(int v, int* ws, int* total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) ws[wid] = x;
-    __syncthreads();
-    if (wid == 0) {
-        int t = lane < BLOCK / 64 ? ws[lane] : 0;
-#pragma unroll
-        for (int o = 1; o < BLOCK / 64; o <<= 1) {
-            const int y = __shfl_up(t, o, 64);
-            if (lane >= o) t += y;
-        }
-        if (lane < BLOCK / 64) ws[lane] = t;
-    }
-    __syncthreads();
-    const int base = wid ? ws[wid - 1] : 0;
-    *total = ws[BLOCK / 64 - 1];
-    __syncthreads();
-    return base + x - v;
-}
 
 // (the batch pipeline's gather + bearings: knn2_merge_kernel since r05, matcher.hip)
 

@@ -32,6 +32,7 @@
 #include "erp_ctx.hpp"
 #include "erp_device.hpp"
 #include "erp_launch.hpp"
+#include "erp_stage.hpp"
 #include "erp_winner.hpp"
 
 using erp::CtxCall;
@@ -42,9 +43,7 @@ using namespace erp;
 
 constexpr int kPolishThreads = kWinnerThreads;  // (winner_from_records' block)
 constexpr int kPolishWaves = kPolishThreads / 64;
-constexpr int kPolishMaxM = 65535;                      // as find: the bitmap's size
-constexpr int kPolishWords = (kPolishMaxM + 63) / 64;   // 64-bit words of one bitmap
-constexpr int kPolishMaxRounds = 8;
+constexpr int kPolishWords = (kStageMaxM + 63) / 64;   // 64-bit words of one bitmap
 constexpr int kPolishMinFit = 9;   // below it the thin-SVD rule applies (erp_match.h)
 
 struct PolishArgs {
@@ -141,24 +140,18 @@ __device__ int polish_pass(const double* Ec_lds, double thr, int M, const erp_po
     return total;
 }
 
+// the pair's round records from round `from` on to zero
+__device__ void polish_zero_rounds(const PolishArgs& a, int p, int from) {
+    if (!a.rounds_out) return;
+    stage_zero<kPolishThreads>((int32_t*)(a.rounds_out + (size_t)p * a.rounds + from),
+                               (a.rounds - from) * (int64_t)(sizeof(erp_polish_round) / 4));
+}
+
 // the pair's outputs when it does not run: the status and zeros
 __device__ void polish_skip(const PolishArgs& a, int p, int32_t status) {
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        erp_polish_result o;
-        memset(&o, 0, sizeof(o));
-        o.status = status;
-        a.out[p] = o;
-    }
-    if (a.rounds_out) {
-        int32_t* w = (int32_t*)(a.rounds_out + (size_t)p * a.rounds);
-        const int n = a.rounds * (int)(sizeof(erp_polish_round) / 4);
-        for (int k = tid; k < n; k += kPolishThreads) w[k] = 0;
-    }
-    if (a.mask) {
-        uint8_t* m = a.mask + (size_t)p * a.in.key_stride;
-        for (int64_t i = tid; i < a.in.key_stride; i += kPolishThreads) m[i] = 0;
-    }
+    if (threadIdx.x == 0) a.out[p] = stage_record<erp_polish_result>(status);
+    polish_zero_rounds(a, p, 0);
+    if (a.mask) stage_zero<kPolishThreads>(a.mask + (size_t)p * a.in.key_stride, a.in.key_stride);
 }
 
 __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
@@ -171,12 +164,12 @@ __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
 
     const int p = blockIdx.x, tid = threadIdx.x;
     const erp_pair_result* res = a.in.results + p;
-    const int32_t status = res->status;
     const int64_t stride = a.in.key_stride;
-    int64_t m64 = res->M;
-    m64 = m64 < 0 ? 0 : (m64 > stride ? stride : m64);
-    if (status != ERP_OK || m64 > kPolishMaxM) {  // (block-uniform)
-        polish_skip(a, p, status != ERP_OK ? status : (int32_t)ERP_INVALID_ARG);
+    const int64_t m64 = stage_match_count(res, stride);
+    const erp_winner* wr = a.winners ? a.winners + p : nullptr;  // (erp_polish_winners_dev)
+    const int32_t gate = stage_gate(res->status, m64, wr ? wr->status : (int32_t)ERP_OK);
+    if (gate != ERP_OK) {  // (block-uniform)
+        polish_skip(a, p, gate);
         return;
     }
     const int M = (int)m64;
@@ -184,12 +177,7 @@ __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
     // ---- the winner: the record whose R1 / R2 was pushed as row min_idx, from the records'
     // flags (erp_winner.hpp) or, for erp_polish_winners_dev, from the pair's winner record ----
     const double* e0;
-    if (a.winners) {  // (block-uniform)
-        const erp_winner* wr = a.winners + p;
-        if (wr->status != ERP_OK) {
-            polish_skip(a, p, wr->status);
-            return;
-        }
+    if (wr) {  // (block-uniform)
         if (tid == 0) {
             win[0] = wr->iter;
             win[1] = wr->which;
@@ -290,14 +278,12 @@ __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
 
     // ---- outputs ----
     if (tid == 0) {
-        erp_polish_result o;
-        memset(&o, 0, sizeof(o));
+        erp_polish_result o = stage_record<erp_polish_result>(ERP_OK);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             o.R[k] = acc.R[k];
             o.T[k] = acc.T[k];
         }
-        o.status = ERP_OK;
         o.winner_iter = winner;
         o.winner_which = winner_which;
         o.rounds_done = done;
@@ -307,11 +293,7 @@ __global__ __launch_bounds__(kPolishThreads) void polish_kernel(PolishArgs a) {
         for (int k = 0; k < 9; k++) o.E[k] = acc.e[k];
         a.out[p] = o;
     }
-    if (a.rounds_out) {
-        int32_t* w = (int32_t*)(a.rounds_out + (size_t)p * a.rounds + done);
-        const int n = (a.rounds - done) * (int)(sizeof(erp_polish_round) / 4);
-        for (int k = tid; k < n; k += kPolishThreads) w[k] = 0;
-    }
+    polish_zero_rounds(a, p, done);
     if (a.mask) {
         uint8_t* m = a.mask + (size_t)p * stride;
         for (int64_t i = tid; i < stride; i += kPolishThreads)
@@ -372,43 +354,29 @@ erp_status erp_eight_point_find_polished(erp_ctx* ctx, int32_t W, int32_t H,
                                          int32_t rounds, erp_pair_result* h_result,
                                          erp_polish_result* h_polish, uint8_t* h_mask) {
     // (the polish's arguments first: a call that fails on them must not consume a rand stream)
-    if (!ctx || !cfg || cfg->iters < 1 || m < 0 || m > kPolishMaxM || (m > 0 && (!h_kl || !h_kr)) ||
+    if (!ctx || !cfg || cfg->iters < 1 || m < 0 || m > kStageMaxM || (m > 0 && (!h_kl || !h_kr)) ||
         !(thr > 0) || rounds < 0 || rounds > kPolishMaxRounds)
         return ERP_INVALID_ARG;
     // one lock across upload, find, polish and download: the staging buffers are the context's
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     ERP_CK(hipSetDevice(ctx->device));
-    const size_t hyp_bytes = (size_t)cfg->iters * sizeof(erp_hypothesis);
-    const size_t host_bytes = hyp_bytes + sizeof(erp_polish_result) + 8 + (size_t)m + 8;
-    if (!erp::ensure(ctx->in_a, (size_t)m * 8 + 8) || !erp::ensure(ctx->in_b, (size_t)m * 8 + 8) ||
-        !erp::ensure(ctx->in_c, sizeof(erp_pair_result)))
-        return ERP_OUT_OF_MEMORY;
-    char* base = erp::ctx_scratch<char>(ctx, erp::kSlotPolishHost, host_bytes);
-    if (!base) return ERP_OUT_OF_MEMORY;
-    erp_hypothesis* d_hyps = (erp_hypothesis*)base;
-    erp_polish_result* d_pol = (erp_polish_result*)(base + hyp_bytes);
-    int32_t* d_wh = (int32_t*)(base + hyp_bytes + sizeof(erp_polish_result));
-    uint8_t* d_mask = (uint8_t*)(d_wh + 2);
-    if (m > 0) {
-        ERP_CK(hipMemcpy(ctx->in_a.p, h_kl, (size_t)m * 8, hipMemcpyHostToDevice));
-        ERP_CK(hipMemcpy(ctx->in_b.p, h_kr, (size_t)m * 8, hipMemcpyHostToDevice));
-    }
+    const PolishedStage L(m, cfg->iters);
+    erp_status s = upload_keys(ctx, h_kl, h_kr, m);
+    if (s != ERP_OK) return s;
+    char* base = ctx_scratch<char>(ctx, kSlotHostStage, L.bytes);
+    if (!base || !ensure(ctx->in_c, sizeof(erp_pair_result))) return ERP_OUT_OF_MEMORY;
+    erp_hypothesis* d_hyps = (erp_hypothesis*)(base + L.hyps);
+    erp_polish_result* d_pol = (erp_polish_result*)(base + L.polish);
+    int32_t* d_wh = (int32_t*)(base + L.wh);
+    uint8_t* d_mask = (uint8_t*)(base + L.mask);
+    erp_pair_result* d_res = (erp_pair_result*)ctx->in_c.p;
     const int32_t wh[2] = {W, H};
     ERP_CK(hipMemcpy(d_wh, wh, sizeof(wh), hipMemcpyHostToDevice));
-    erp_pair_result* d_res = (erp_pair_result*)ctx->in_c.p;
-    erp_status s = erp_eight_point_find_dev(ctx, W, H, (const erp_point2f*)ctx->in_a.p,
-                                            (const erp_point2f*)ctx->in_b.p, m, cfg, d_res, d_hyps,
-                                            nullptr);
+    s = erp_eight_point_find_dev(ctx, W, H, keys_left(ctx), keys_right(ctx), m, cfg, d_res, d_hyps,
+                                 nullptr);
     if (s != ERP_OK) return s;
-    erp_polish_inputs in{};
-    in.n_pairs = 1;
+    erp_polish_inputs in = one_pair_inputs<erp_polish_inputs>(ctx, m, d_wh, d_res);
     in.iters = cfg->iters;
-    in.key_stride = m;
-    in.key_left = (const erp_point2f*)ctx->in_a.p;
-    in.key_right = (const erp_point2f*)ctx->in_b.p;
-    in.width = d_wh;
-    in.height = d_wh + 1;
-    in.results = d_res;
     in.hyps = d_hyps;
     s = erp_polish_dev(ctx, &in, cfg->valid_abs, thr, rounds, d_pol, nullptr, d_mask, nullptr);
     if (s != ERP_OK) return s;

@@ -30,6 +30,7 @@
 #include "erp_ctx.hpp"
 #include "erp_device.hpp"
 #include "erp_launch.hpp"
+#include "erp_stage.hpp"
 
 using erp::CtxCall;
 
@@ -39,8 +40,6 @@ using namespace erp;
 
 constexpr int kPoseThreads = 256;
 constexpr int kPoseWaves = kPoseThreads / 64;
-constexpr int kPoseMaxM = 65535;   // as find and the polish
-constexpr int kPoseMaxRounds = 8;  // (erp_polish_winners_dev's limit, for find_posed's check)
 
 struct PoseArgs {
     erp_pose_inputs in;
@@ -89,49 +88,32 @@ __device__ __forceinline__ bool pose_match(const PoseArgs& a, const PoseCand& cd
     return ok;
 }
 
-// the pair's result record into results_out: every byte copied (as eight 64-bit words), R and T
-// -- the record's first six floats -- replaced when given
-static_assert(sizeof(erp_pair_result) == 64 && offsetof(erp_pair_result, R) == 0 &&
-                  offsetof(erp_pair_result, T) == 12,
-              "pose_copy_result patches words 0..2");
+// the pair's result record into results_out, R and T replaced when given
 __device__ __forceinline__ void pose_copy_result(const PoseArgs& a, int p, const float* R,
                                                  const float* T) {
     if (!a.results_out || threadIdx.x != 0) return;
-    const uint64_t* src = (const uint64_t*)(a.in.results + p);
-    uint64_t* dst = (uint64_t*)(a.results_out + p);
-    uint64_t w[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) w[k] = src[k];
-    if (R) {
+    copy_result(a.results_out + p, a.in.results + p, [=](uint64_t* w) {
+        if (!R) return;
         const uint32_t f[6] = {__float_as_uint(R[0]), __float_as_uint(R[1]), __float_as_uint(R[2]),
                                __float_as_uint(T[0]), __float_as_uint(T[1]), __float_as_uint(T[2])};
 #pragma unroll
         for (int k = 0; k < 3; k++) w[k] = (uint64_t)f[2 * k] | ((uint64_t)f[2 * k + 1] << 32);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; k++) dst[k] = w[k];
+    });
 }
 
 // depth and front of slots [from, key_stride) to zero
 __device__ __forceinline__ void pose_zero_tail(const PoseArgs& a, int p, int64_t from) {
     const int64_t stride = a.in.key_stride;
-    if (a.depth) {
-        double* d = a.depth + (size_t)p * stride * 2;
-        for (int64_t i = 2 * from + threadIdx.x; i < 2 * stride; i += kPoseThreads) d[i] = 0.0;
-    }
-    if (a.front) {
-        uint8_t* f = a.front + (size_t)p * stride;
-        for (int64_t i = from + threadIdx.x; i < stride; i += kPoseThreads) f[i] = 0;
-    }
+    if (a.depth)
+        stage_zero<kPoseThreads>(a.depth + ((size_t)p * stride + from) * 2, 2 * (stride - from));
+    if (a.front) stage_zero<kPoseThreads>(a.front + (size_t)p * stride + from, stride - from);
 }
 
 // the pair's outputs when no pose is selected: the status and zeros, the result record as it is
 __device__ __forceinline__ void pose_skip(const PoseArgs& a, int p, int32_t status, const int* votes,
                           int n_voters) {
     if (threadIdx.x == 0) {
-        erp_pose o;
-        memset(&o, 0, sizeof(o));
-        o.status = status;
+        erp_pose o = stage_record<erp_pose>(status);
         if (votes) {
 #pragma unroll
             for (int k = 0; k < 4; k++) o.votes[k] = votes[k];
@@ -149,27 +131,19 @@ __global__ __launch_bounds__(kPoseThreads) void pose_kernel(PoseArgs a) {
 
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const erp_pair_result* res = a.in.results + p;
-    const int32_t status = res->status;
     const int64_t stride = a.in.key_stride;
-    int64_t m64 = res->M;
-    m64 = m64 < 0 ? 0 : (m64 > stride ? stride : m64);
-    if (status != ERP_OK || m64 > kPoseMaxM) {  // (block-uniform, as every branch on a status)
-        pose_skip(a, p, status != ERP_OK ? status : (int32_t)ERP_INVALID_ARG, nullptr, 0);
+    const int64_t m64 = stage_match_count(res, stride);
+    const RecordSource src = source_of(a.in);
+    const int32_t gate = stage_gate(res->status, m64, src.status_of(p));
+    if (gate != ERP_OK) {  // (block-uniform, as every branch on a status)
+        pose_skip(a, p, gate, nullptr, 0);
         return;
-    }
-    if (a.in.src_status) {
-        const int32_t ss = *(const int32_t*)((const char*)a.in.src_status +
-                                             (size_t)p * a.in.src_status_stride);
-        if (ss != ERP_OK) {
-            pose_skip(a, p, ss, nullptr, 0);
-            return;
-        }
     }
     const int M = (int)m64;
 
     // ---- candidates (rule 1) ----
     if (tid == 0) {
-        const double* e = (const double*)((const char*)a.in.e + (size_t)p * a.in.e_stride);
+        const double* e = src.e_of(p);
         double e9[9];
 #pragma unroll
         for (int k = 0; k < 9; k++) e9[k] = e[k];
@@ -232,9 +206,7 @@ __global__ __launch_bounds__(kPoseThreads) void pose_kernel(PoseArgs a) {
 
     // ---- the record (rule 5) ----
     if (tid == 0) {
-        erp_pose o;
-        memset(&o, 0, sizeof(o));
-        o.status = ERP_OK;
+        erp_pose o = stage_record<erp_pose>(ERP_OK);
         o.which = which;
         o.t_sign = neg ? -1 : 1;
         o.n_voters = tot[4];
@@ -298,11 +270,8 @@ erp_status erp_pose_select_dev(erp_ctx* ctx, const erp_pose_inputs* in, float th
         in->key_stride < 0)
         return ERP_INVALID_ARG;
     if (in->n_pairs == 0) return ERP_OK;
-    if (!d_out || !in->results || !in->e || !in->width || !in->height ||
-        (in->key_stride > 0 && (!in->key_left || !in->key_right)) || in->e_stride < 0 ||
-        (in->e_stride & 7) != 0 || ((uintptr_t)in->e & 7) != 0 ||
-        (in->src_status && (in->src_status_stride < 0 || (in->src_status_stride & 3) != 0 ||
-                            ((uintptr_t)in->src_status & 3) != 0)))
+    if (!d_out || !in->results || !in->width || !in->height ||
+        (in->key_stride > 0 && (!in->key_left || !in->key_right)) || !source_ok(source_of(*in)))
         return ERP_INVALID_ARG;
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
@@ -326,59 +295,36 @@ erp_status erp_eight_point_find_posed(erp_ctx* ctx, int32_t W, int32_t H, const 
                                       erp_polish_result* h_polish, erp_pose* h_pose,
                                       uint8_t* h_mask, double* h_depth, uint8_t* h_front) {
     // (the later stages' arguments first: a call that fails on them must not consume a rand stream)
-    if (!ctx || !cfg || cfg->iters < 1 || m < 0 || m > kPoseMaxM || (m > 0 && (!h_kl || !h_kr)) ||
-        !(thr > 0) || rounds < 0 || rounds > kPoseMaxRounds || !(min_sin2 >= 0))
+    if (!ctx || !cfg || cfg->iters < 1 || m < 0 || m > kStageMaxM || (m > 0 && (!h_kl || !h_kr)) ||
+        !(thr > 0) || rounds < 0 || rounds > kPolishMaxRounds || !(min_sin2 >= 0))
         return ERP_INVALID_ARG;
     // one lock across upload, find, polish, selection and download: the staging buffers are the
     // context's
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     ERP_CK(hipSetDevice(ctx->device));
-    // the device side behind the keypoints: result, winner, polish and pose records, W / H, the
-    // depths (8-byte aligned up to here), then the polish's mask and front
-    const size_t o_win = sizeof(erp_pair_result), o_pol = o_win + sizeof(erp_winner),
-                 o_pose = o_pol + sizeof(erp_polish_result), o_wh = o_pose + sizeof(erp_pose),
-                 o_depth = o_wh + 8, o_mask = o_depth + (size_t)m * 16, o_front = o_mask + (size_t)m;
-    if (!erp::ensure(ctx->in_a, (size_t)m * 8 + 8) || !erp::ensure(ctx->in_b, (size_t)m * 8 + 8))
-        return ERP_OUT_OF_MEMORY;
-    char* base = erp::ctx_scratch<char>(ctx, erp::kSlotPoseHost, o_front + (size_t)m + 8);
+    const PosedStage L(m);
+    erp_status s = upload_keys(ctx, h_kl, h_kr, m);
+    if (s != ERP_OK) return s;
+    char* base = ctx_scratch<char>(ctx, kSlotHostStage, L.bytes);
     if (!base) return ERP_OUT_OF_MEMORY;
-    erp_pair_result* d_res = (erp_pair_result*)base;
-    erp_winner* d_win = (erp_winner*)(base + o_win);
-    erp_polish_result* d_pol = (erp_polish_result*)(base + o_pol);
-    erp_pose* d_pose = (erp_pose*)(base + o_pose);
-    int32_t* d_wh = (int32_t*)(base + o_wh);
-    double* d_depth = (double*)(base + o_depth);
-    uint8_t* d_mask = (uint8_t*)(base + o_mask);
-    uint8_t* d_front = (uint8_t*)(base + o_front);
-    if (m > 0) {
-        ERP_CK(hipMemcpy(ctx->in_a.p, h_kl, (size_t)m * 8, hipMemcpyHostToDevice));
-        ERP_CK(hipMemcpy(ctx->in_b.p, h_kr, (size_t)m * 8, hipMemcpyHostToDevice));
-    }
+    erp_pair_result* d_res = (erp_pair_result*)(base + L.result);
+    erp_winner* d_win = (erp_winner*)(base + L.winner);
+    erp_polish_result* d_pol = (erp_polish_result*)(base + L.polish);
+    erp_pose* d_pose = (erp_pose*)(base + L.pose);
+    int32_t* d_wh = (int32_t*)(base + L.wh);
+    double* d_depth = (double*)(base + L.depth);
+    uint8_t* d_mask = (uint8_t*)(base + L.mask);
+    uint8_t* d_front = (uint8_t*)(base + L.front);
     const int32_t wh[2] = {W, H};
     ERP_CK(hipMemcpy(d_wh, wh, sizeof(wh), hipMemcpyHostToDevice));
-    erp_status s = erp_eight_point_find_winner_dev(ctx, W, H, (const erp_point2f*)ctx->in_a.p,
-                                                   (const erp_point2f*)ctx->in_b.p, m, cfg, d_res,
-                                                   nullptr, d_win, nullptr);
+    s = erp_eight_point_find_winner_dev(ctx, W, H, keys_left(ctx), keys_right(ctx), m, cfg, d_res,
+                                        nullptr, d_win, nullptr);
     if (s != ERP_OK) return s;
-    erp_polish_inputs pin{};
-    pin.n_pairs = 1;
-    pin.key_stride = m;
-    pin.key_left = (const erp_point2f*)ctx->in_a.p;
-    pin.key_right = (const erp_point2f*)ctx->in_b.p;
-    pin.width = d_wh;
-    pin.height = d_wh + 1;
-    pin.results = d_res;
+    const erp_polish_inputs pin = one_pair_inputs<erp_polish_inputs>(ctx, m, d_wh, d_res);
     s = erp_polish_winners_dev(ctx, &pin, d_win, cfg->valid_abs, thr, rounds, d_pol, nullptr,
                                d_mask, nullptr);
     if (s != ERP_OK) return s;
-    erp_pose_inputs in{};
-    in.n_pairs = 1;
-    in.key_stride = m;
-    in.key_left = pin.key_left;
-    in.key_right = pin.key_right;
-    in.width = d_wh;
-    in.height = d_wh + 1;
-    in.results = d_res;
+    erp_pose_inputs in = one_pair_inputs<erp_pose_inputs>(ctx, m, d_wh, d_res);
     in.e = d_pol->E;
     in.e_stride = sizeof(erp_polish_result);
     in.src_status = &d_pol->status;

@@ -28,6 +28,7 @@
 #include "erp_device.hpp"
 #include "erp_kernels.hpp"
 #include "erp_launch.hpp"
+#include "erp_stage.hpp"
 #include "erp_winner.hpp"
 
 namespace erp {
@@ -38,11 +39,7 @@ constexpr double kWinnerGramScale = 0x1p44;  // gram_limbs_kernel's fixed point 
 
 // the pair's record when it has no winner: the status and zeros
 __device__ void winner_none(const WinnerArgs& a, int p, int32_t status) {
-    if (threadIdx.x != 0) return;
-    erp_winner o;
-    memset(&o, 0, sizeof(o));
-    o.status = status;
-    a.out[p] = o;
+    if (threadIdx.x == 0) a.out[p] = stage_record<erp_winner>(status);
 }
 
 // the lite route's locate (wave 0 only): win as winner_from_records leaves it
@@ -53,7 +50,7 @@ __device__ void winner_from_lite(const float* hl, const int32_t* vw, int iters, 
     for (int w0 = 0; w0 < nwaves; w0 += 64) {  // (every bound below is wave-uniform)
         const int w = w0 + lane;
         const int c = w < nwaves ? vw[(size_t)w * 8] : 0;
-        const int x = winner_wave_scan(c, lane);
+        const int x = wave_inclusive_scan(c, lane);
         const int first = base + x - c;  // the row the wave's first valid rotation got
         const uint64_t hit = __ballot(c > 0 && min_idx >= first && min_idx < first + c);
         if (hit) {
@@ -72,7 +69,7 @@ __device__ void winner_from_lite(const float* hl, const int32_t* vw, int iters, 
         v1 = !__builtin_isnan(hl[h]);
         c = v1 + !__builtin_isnan(hl[(size_t)3 * iters + h]);
     }
-    const int x = winner_wave_scan(c, lane);
+    const int x = wave_inclusive_scan(c, lane);
     const int first = wfirst + x - c;
     if (c && min_idx >= first && min_idx < first + c) {
         win[0] = h;
@@ -183,9 +180,7 @@ __global__ __launch_bounds__(kWinnerThreads) void winner_kernel(WinnerArgs a) {
     for (int k = 0; k < 3; k++)
         same = same && __float_as_uint(R[k]) == __float_as_uint(res->R[k]) &&
                __float_as_uint(hy.T[k]) == __float_as_uint(res->T[k]);
-    erp_winner o;
-    memset(&o, 0, sizeof(o));
-    o.status = same ? ERP_OK : ERP_INTERNAL;
+    erp_winner o = stage_record<erp_winner>(same ? ERP_OK : ERP_INTERNAL);
     if (same) {
         o.iter = winner;
         o.which = which;

@@ -491,3 +491,52 @@ def test_host_entry_point_and_cpp_driver_give_the_device_list(ctx, oracle, ragge
                                p["H"], p["e"], thr=0.01)) == 0
     assert len(fm.match_guided(p["desc_l"], p["desc_r"][:0], p["kp_l"], p["kp_r"][:0], p["W"],
                                p["H"], p["e"], thr=0.01)) == 0
+
+
+# ------------------------------------------------------------- 8. the shared host staging slot
+def test_host_entry_points_share_one_staging_slot(gpu_lib, oracle):
+    """erp_match_guided, erp_eight_point_find_posed and erp_eight_point_find_polished stage
+    through one scratch slot of the context.  Back to back on ONE context, with sizes that grow
+    the slot and then use less of it -- match_guided (40, 40), find_posed m = 700, find_polished
+    m = 9, match_guided (40, 40) again --, every output equals, byte for byte, the same call on a
+    fresh context: a wrong size or a stale pointer in the shared slot would show here.  80
+    iterations, the default seed / offset, no rand stream."""
+    from erp_match_eightpoint_test_amd import (Context, ErpError, eight_point, feature_matcher,
+                                               synth)
+    g, e = GR.pair_e(oracle, 28, 40, 0.03)
+    assert len(g["desc_l"]) == 40 and len(g["desc_r"]) == 40
+    p = synth.make_pair(41, n_kpts=1024)
+    idx = np.flatnonzero(p["gt_partner"] >= 0)[:700]
+    assert len(idx) == 700
+    kl, kr = p["kp_l"][idx], p["kp_r"][p["gt_partner"][idx]]
+    thr = 0.01
+
+    def guided(c):
+        m = feature_matcher(ctx=c).match_guided(g["desc_l"], g["desc_r"], g["kp_l"], g["kp_r"],
+                                                g["W"], g["H"], e, thr=thr)
+        return [m.tobytes()]
+
+    def posed(c):
+        ep = eight_point(ctx=c, iters=80)
+        ret = ep.find_posed(p["W"], p["H"], kl, kr, thr, 3)
+        assert ep.last_pose["status"] == 0
+        return [a.tobytes() for a in (*ret, ep.last_result, ep.last_polish, ep.last_pose)]
+
+    def polished(c):
+        ep = eight_point(ctx=c, iters=80)
+        try:   # (nine matches: whatever find makes of them, the records are compared)
+            ret = ep.find_polished(p["W"], p["H"], kl[:9], kr[:9], thr, 3)
+        except ErpError as err:
+            ret = (np.int32(err.status),)
+        return [a.tobytes() for a in (*ret, ep.last_result, ep.last_polish)]
+
+    calls = (guided, posed, polished, guided)
+    shared = Context(0)
+    got = [f(shared) for f in calls]
+    assert len(np.frombuffer(got[0][0], np.uint8)) > 0   # (the guided list is not empty)
+    for k, f in enumerate(calls):
+        fresh = Context(0)
+        assert f(fresh) == got[k], f.__name__
+        fresh.close()
+    assert got[3] == got[0]
+    shared.close()
