@@ -27,15 +27,15 @@ import numpy as np
 
 from . import capi, synth
 from .capi import (DMATCH_DTYPE, HYP_DTYPE, POLISH_DTYPE, POLISH_ROUND_DTYPE, POSE_DTYPE, RESULT_DTYPE,
-                   WINNER_DTYPE, Context, ErpError, RandStream, check, default_cfg,
-                   process_rand_stream)
+                   SUPPORT_DTYPE, WINNER_DTYPE, Context, ErpError, RandStream, check, default_cfg,
+                   process_rand_stream, support_to_numpy)
 
 __all__ = ["feature_matcher", "eight_point", "erp_rotation", "spherical_surf", "epipolar_tool",
            "PairBatchRunner", "Context", "ErpError", "RandStream", "process_rand_stream",
            "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "POLISH_DTYPE",
            "POLISH_ROUND_DTYPE", "WINNER_DTYPE", "results_to_numpy", "hyps_to_numpy",
            "polish_to_numpy", "polish_rounds_to_numpy", "winners_to_numpy", "sweep_relative_rotation", "synth", "capi",
-           "POSE_DTYPE", "pose_to_numpy"]
+           "POSE_DTYPE", "pose_to_numpy", "SUPPORT_DTYPE", "support_to_numpy"]
 
 
 def _np_ptr(a: np.ndarray):
@@ -202,6 +202,16 @@ def _keys(key_left, key_right, match_size):
     return np.ascontiguousarray(kl[:m]), np.ascontiguousarray(kr[:m]), m
 
 
+def _support_thr(thr) -> float:
+    """the support stage's threshold as the C float: finite and > 0, checked before any call"""
+    if thr is None:
+        raise ValueError("the support stage needs a threshold (support_thr / thr > 0)")
+    t = float(np.float32(thr))
+    if not (np.isfinite(t) and t > 0.0):
+        raise ValueError(f"support threshold must be finite and > 0, got {thr!r}")
+    return t
+
+
 def _record(struct, dtype):
     """a ctypes record as a numpy scalar of its structured dtype"""
     return np.frombuffer(bytes(struct), dtype)[0]
@@ -221,6 +231,9 @@ class eight_point:  # noqa: N801  (reference class name)
         self.last_polish = None
         self.last_winner = None
         self.last_pose = None
+        self.last_support = None
+        self.last_support_result = None
+        self.last_counts = None
         if stream is not None:
             self.ctx.set_rand_stream(stream)
 
@@ -255,6 +268,38 @@ class eight_point:  # noqa: N801  (reference class name)
         self.last_winner = _record(win, WINNER_DTYPE)
         check(st, "find_winner")
         check(int(self.last_winner["status"]), "find_winner: winner record")
+        return R, T, self.last_winner["E"].reshape(3, 3).copy()
+
+    def find_support(self, im_width: int, im_height: int, key_left, key_right, thr: float,
+                     match_size: int | None = None, want_counts: bool = False):
+        """find plus the support stage (erp_eight_point_find_support; no reference counterpart)
+        -> (R (3,), T (3,), E (3, 3) float64) of the scored iteration that most matches agree
+        with under |l^T E' r| < thr (the first such iteration on ties), instead of the consensus
+        winner find returns.  It pays with minimal samples (``sample_frac`` chosen for about 10
+        rows), not at the reference's 0.25.  ``last_result`` is find's own
+        record, ``last_support`` the support record (SUPPORT_DTYPE: status, iter, which, inliers,
+        scored, consensus_iter, consensus_inliers, row), ``last_winner`` that iteration's winner
+        record, ``last_support_result`` find's record with R, T and min_idx replaced, and
+        ``last_counts`` (want_counts) every iteration's inlier count.  Consumes a rand stream
+        exactly as find does."""
+        thr = _support_thr(thr)
+        kl, kr, m = _keys(key_left, key_right, match_size)
+        R = np.zeros(3, np.float32)
+        T = np.zeros(3, np.float32)
+        res, sres = capi.PairResult(), capi.PairResult()
+        sup, win = capi.Support(), capi.Winner()
+        counts = np.zeros(max(self.cfg.iters, 1), np.int32) if want_counts else None
+        st = self.ctx.L.erp_eight_point_find_support(
+            self.ctx.h, im_width, im_height, _np_ptr(kl), _np_ptr(kr), m, C.byref(self.cfg), thr,
+            _np_ptr(R), _np_ptr(T), C.byref(res), C.byref(sup), C.byref(win), C.byref(sres),
+            _np_ptr(counts) if want_counts else None)
+        self.last_result = _record(res, RESULT_DTYPE)
+        self.last_support = _record(sup, SUPPORT_DTYPE)
+        self.last_winner = _record(win, WINNER_DTYPE)
+        self.last_support_result = _record(sres, RESULT_DTYPE)
+        self.last_counts = counts[:self.cfg.iters] if want_counts else None
+        check(st, "find_support")
+        check(int(self.last_support["status"]), "find_support: support record")
         return R, T, self.last_winner["E"].reshape(3, 3).copy()
 
     def find_polished(self, im_width: int, im_height: int, key_left, key_right, thr: float,
@@ -959,7 +1004,11 @@ class PairBatchRunner:
     returns a torch uint8 tensor of erp_pair_result records (view with RESULT_DTYPE after
     .cpu()).  Optional debug outputs (matches, hyps, samples, rvec, tvec, dist) are allocated
     when requested; want=("winners",) adds the winner records (uint8 [P, 88], WINNER_DTYPE: the
-    winning iteration's E without the hypothesis records) through erp_pair_batch_run_winners.
+    winning iteration's E without the hypothesis records) through erp_pair_batch_run_winners;
+    want=("support",) with support_thr= adds the support stage (erp_pair_batch_run_support): the
+    scored iteration most matches agree with under |l^T E' r| < support_thr, as "support" (uint8
+    [P, 32], SUPPORT_DTYPE), "support_winners" (uint8 [P, 88]), "support_results" (uint8 [P, 64])
+    and, with want "support_counts", every iteration's count (int32 [P, iters]).
     """
 
     def __init__(self, device: int = 0, ctx: Context | None = None, reuse_outputs: bool = False,
@@ -983,8 +1032,18 @@ class PairBatchRunner:
               "erp_ctx_reserve")
 
     def run(self, desc_l, desc_r, kp_l, kp_r, off_l, off_r, width, height, max_nq: int,
-            max_nt: int, ratio: float = 0.3, want=(), stream=None):
+            max_nt: int, ratio: float = 0.3, want=(), stream=None, support_thr=None):
         import torch
+        want = tuple(want)
+        if "support_counts" in want and "support" not in want:
+            raise ValueError("want 'support_counts' needs 'support'")
+        if "support" in want and "winners" in want:
+            raise ValueError("want 'support' or 'winners', not both: one stage per run "
+                             "(out['support_winners'] holds the support stage's winner records)")
+        if "support" in want:
+            support_thr = _support_thr(support_thr)
+        elif support_thr is not None:
+            raise ValueError("support_thr needs want=('support', ...)")
         n_pairs = off_l.shape[0] - 1
         dev = desc_l.device
         for t, dt in ((desc_l, torch.float32), (desc_r, torch.float32), (kp_l, torch.float32),
@@ -998,7 +1057,7 @@ class PairBatchRunner:
         key = (n_pairs, max_nq, tuple(want), str(dev), self.cfg.iters)
         if self.reuse_outputs and key in self._outs:
             outs = self._outs[key]
-            return self._launch(b, ratio, outs, stream, dev)
+            return self._launch(b, ratio, outs, stream, dev, support_thr)
         outs = {"results": torch.empty((n_pairs, RESULT_DTYPE.itemsize), dtype=torch.uint8,
                                        device=dev)}
         iters = self.cfg.iters
@@ -1011,13 +1070,29 @@ class PairBatchRunner:
                   "rvec": (n_pairs, 2 * iters, 3, torch.float32),
                   "tvec": (n_pairs, 2 * iters, 3, torch.float32),
                   "dist": (n_pairs, 2 * iters, torch.float64),
-                  "winners": (n_pairs, WINNER_DTYPE.itemsize, torch.uint8)}
+                  "winners": (n_pairs, WINNER_DTYPE.itemsize, torch.uint8),
+                  "support": (n_pairs, SUPPORT_DTYPE.itemsize, torch.uint8),
+                  "support_counts": (n_pairs, iters, torch.int32)}
+        if "support" in want:
+            outs["support_winners"] = torch.zeros((n_pairs, WINNER_DTYPE.itemsize),
+                                                  dtype=torch.uint8, device=dev)
+            outs["support_results"] = torch.zeros((n_pairs, RESULT_DTYPE.itemsize),
+                                                  dtype=torch.uint8, device=dev)
         for name in want:
             *shape, dt = shapes[name]
             outs[name] = torch.zeros(shape, dtype=dt, device=dev)
         if self.reuse_outputs:
             self._outs[key] = outs
-        return self._launch(b, ratio, outs, stream, dev)
+        return self._launch(b, ratio, outs, stream, dev, support_thr)
+
+    @staticmethod
+    def support_view(out: dict) -> dict:
+        """run(..., want=("support", ...))'s dict with the support stage's records in the
+        consensus winner's place: {**out, "results": support_results, "winners":
+        support_winners}, which polish(), select_pose() and guided_match() take unchanged."""
+        if "support_results" not in out or "support_winners" not in out:
+            raise ValueError("support_view needs run(..., want=('support', ...))")
+        return {**out, "results": out["support_results"], "winners": out["support_winners"]}
 
     def run_images(self, lefts, rights, ratio: float = 0.3, want=(), max_kp: int = 16384,
                    fill: int = 0, max_group_pairs: int = 0, **surf_params):
@@ -1194,7 +1269,7 @@ class PairBatchRunner:
                                      thr=thr, ratio=ratio, max_dist=max_dist, unique=unique,
                                      want=want, stream=stream)
 
-    def _launch(self, b, ratio, outs, stream, dev):
+    def _launch(self, b, ratio, outs, stream, dev, support_thr=None):
         import torch
         o = capi.BatchOutputs(*[outs[k].data_ptr() if k in outs else None
                                 for k in ("results", "matches", "key_left", "key_right", "hyps",
@@ -1205,6 +1280,16 @@ class PairBatchRunner:
                                                         C.byref(self.cfg), C.byref(o),
                                                         outs["winners"].data_ptr(), st),
                   "erp_pair_batch_run_winners")
+            return outs
+        if "support" in outs:
+            so = capi.SupportOutputs(outs["support"].data_ptr(), outs["support_winners"].data_ptr(),
+                                     outs["support_results"].data_ptr(),
+                                     outs["support_counts"].data_ptr()
+                                     if "support_counts" in outs else None)
+            check(self.ctx.L.erp_pair_batch_run_support(self.ctx.h, C.byref(b), ratio,
+                                                        C.byref(self.cfg), C.byref(o), support_thr,
+                                                        C.byref(so), st),
+                  "erp_pair_batch_run_support")
             return outs
         check(self.ctx.L.erp_pair_batch_run(self.ctx.h, C.byref(b), ratio, C.byref(self.cfg),
                                             C.byref(o), st), "erp_pair_batch_run")

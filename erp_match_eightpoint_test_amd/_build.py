@@ -21,7 +21,7 @@ ARCH = os.environ.get("ERP_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip", "surf.hip", "surf_api.hip", "viz.hip",
            "image_batch.hip", "rand_stream.hip", "sweep.hip", "polish.hip", "winner.hip", "pose.hip",
-           "guided.hip",
+           "guided.hip", "support.hip",
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
            "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp", "erp_ctx.hpp", "erp_winner.hpp",
@@ -57,7 +57,11 @@ def _run_filtered(cmd):
 # per-source extras: the matcher's MFMA accumulators in VGPRs (the filter's bounds read them
 # directly; the default AGPR form costs one v_accvgpr_read per element) and no NaN quieting in
 # its min trees (finite descriptors; matcher.hip header)
-EXTRA_FLAGS = {"matcher.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"]}
+EXTRA_FLAGS = {"matcher.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
+               # the support count's epilogue compares the accumulators where they are; without
+               # the SLP vectorizer the bf16 packing of its operand images stays free of
+               # v_pk_mov_b32 (the feature flag above does not cover that instruction)
+               "support.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-slp-vectorize"]}
 
 
 def _inputs():
@@ -118,6 +122,7 @@ DRIVERS = {
     "winner": "winner_driver",       # erp::eight_point::find_winner
     "pose": "pose_driver",           # erp::eight_point::find_posed
     "guided": "guided_driver",       # erp::feature_matcher::match_guided
+    "support": "support_driver",     # erp::eight_point::find_support
 }
 
 

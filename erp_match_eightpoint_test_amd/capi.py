@@ -91,6 +91,16 @@ class Winner(C.Structure):
                 ("sample_n", C.c_int32), ("E", C.c_double * 9)]
 
 
+class Support(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iter", C.c_int32), ("which", C.c_int32),
+                ("inliers", C.c_int32), ("scored", C.c_int32), ("consensus_iter", C.c_int32),
+                ("consensus_inliers", C.c_int32), ("row", C.c_int32)]
+
+
+class SupportOutputs(C.Structure):
+    _fields_ = [("support", P), ("winners", P), ("results", P), ("counts", P)]
+
+
 class Pose(C.Structure):
     _fields_ = [("status", C.c_int32), ("which", C.c_int32), ("t_sign", C.c_int32),
                 ("n_voters", C.c_int32), ("votes", C.c_int32 * 4), ("rot_agrees", C.c_int32),
@@ -137,16 +147,29 @@ POLISH_DTYPE = np.dtype([("R", "<f4", 3), ("T", "<f4", 3), ("status", "<i4"),
                         align=True)
 WINNER_DTYPE = np.dtype([("status", "<i4"), ("iter", "<i4"), ("which", "<i4"), ("sample_n", "<i4"),
                          ("E", "<f8", 9)], align=True)
+SUPPORT_DTYPE = np.dtype([("status", "<i4"), ("iter", "<i4"), ("which", "<i4"), ("inliers", "<i4"),
+                          ("scored", "<i4"), ("consensus_iter", "<i4"),
+                          ("consensus_inliers", "<i4"), ("row", "<i4")], align=True)
 POSE_DTYPE = np.dtype([("status", "<i4"), ("which", "<i4"), ("t_sign", "<i4"), ("n_voters", "<i4"),
                        ("votes", "<i4", 4), ("rot_agrees", "<i4"), ("t_flipped", "<i4"),
                        ("R", "<f4", 3), ("T", "<f4", 3), ("Rm", "<f8", 9), ("t", "<f8", 3)],
                       align=True)
 POLISH_MAX_ROUNDS = 8
+
+
+def support_to_numpy(t) -> np.ndarray:
+    """erp_support records (PairBatchRunner.run(..., want=("support",)) "support": a torch uint8
+    tensor [P, 32], or a numpy array of those bytes) -> [P] of SUPPORT_DTYPE"""
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.ascontiguousarray(t)
+    return a.view(SUPPORT_DTYPE).reshape(-1)
+
+
 assert POSE_DTYPE.itemsize == C.sizeof(Pose) == 160
 assert C.sizeof(PoseInputs) == 96
 assert C.sizeof(GuidedCfg) == 16 and C.sizeof(GuidedInputs) == 120 and \
     C.sizeof(GuidedOutputs) == 56
 assert WINNER_DTYPE.itemsize == C.sizeof(Winner) == 88
+assert SUPPORT_DTYPE.itemsize == C.sizeof(Support) == 32 and C.sizeof(SupportOutputs) == 32
 assert DMATCH_DTYPE.itemsize == C.sizeof(DMatch) == 16
 assert POLISH_ROUND_DTYPE.itemsize == C.sizeof(PolishRound) == 112
 assert POLISH_DTYPE.itemsize == C.sizeof(PolishResult) == 120
@@ -181,7 +204,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_polish_dev", "erp_eight_point_find_polished", "erp_pair_batch_run_winners",
             "erp_eight_point_find_winner_dev", "erp_eight_point_find_winner",
             "erp_polish_winners_dev", "erp_pose_select_dev", "erp_eight_point_find_posed",
-            "erp_match_guided_dev", "erp_match_guided"]
+            "erp_match_guided_dev", "erp_match_guided", "erp_pair_batch_run_support",
+            "erp_eight_point_find_support_dev", "erp_eight_point_find_support"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -190,7 +214,8 @@ STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eige
 OPTIONS = {"small_batch": 0, "sampler_lat": 1, "sampler_split": 2, "gram_tiles": 3,
            "zoom_levels": 4, "small_zoom": 5, "lip2": 6, "lipg": 7, "refine_hint": 8,
            "flat_refs": 9, "bound_ratio": 10, "debug_stages": 11, "debug_snap": 12,
-           "sampler_tiers": 13, "vertical_shared": 14, "sampler_share": 15}
+           "sampler_tiers": 13, "vertical_shared": 14, "sampler_share": 15,
+           "support_count": 16}
 MATCHER_MFMA_FILTER = 0  # erp_matcher_method
 MATCHER_VALU_EXACT = 1
 
@@ -364,6 +389,15 @@ def load(build_if_missing: bool = False):
                                               C.POINTER(RansacCfg), P, P, P, P]
     L.erp_polish_winners_dev.argtypes = [P, C.POINTER(PolishInputs), P, C.c_double, C.c_float,
                                          C.c_int32, P, P, P, P]
+    L.erp_pair_batch_run_support.argtypes = [P, C.POINTER(PairBatch), C.c_float,
+                                             C.POINTER(RansacCfg), C.POINTER(BatchOutputs),
+                                             C.c_float, C.POINTER(SupportOutputs), P]
+    L.erp_eight_point_find_support_dev.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
+                                                   C.POINTER(RansacCfg), P, P, C.c_float,
+                                                   C.POINTER(SupportOutputs), P]
+    L.erp_eight_point_find_support.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,
+                                               C.POINTER(RansacCfg), C.c_float, P, P, P, P, P, P,
+                                               P]
     L.erp_pose_select_dev.argtypes = [P, C.POINTER(PoseInputs), C.c_float, C.c_double, P, P, P, P,
                                       P]
     L.erp_eight_point_find_posed.argtypes = [P, C.c_int32, C.c_int32, P, P, C.c_int32,

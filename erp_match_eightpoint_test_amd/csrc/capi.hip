@@ -688,6 +688,67 @@ erp_status run_winners(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_c
     return ERP_OK;
 }
 
+// The support stage behind run_estimator (support.hip; include/erp_match.h "support-scored
+// winner"): four launches over what the run left in the scratch.  As for run_winners, nothing
+// between the estimate and the end of run_consensus writes what it reads.  Checked in
+// run_consensus and ConsensusBufs: counts, flags and hlite are the consensus' inputs only
+// (launch_valid_place / launch_valid_compact read hl / the records into rv, tv); gfin (the lite
+// route's evec), gram and pts are not among ConsensusBufs' buffers, and no launch_consensus_*
+// takes them.  So evec, gram, hl, wsum, counts and pts hold at the end of the consensus what the
+// estimate read and wrote.  (On the lite route gram holds a pair's Grams only where the fused
+// Gram kernel stored them: pairs with s < 9 and the lanes whose evec[0] is NaN -- exactly where
+// the prep reads it.)  The callers refuse a partial ERP_OPT_DEBUG_STAGES mask.
+struct SupportCall {
+    float thr = 0.0f;
+    const erp_support_outputs* out = nullptr;
+};
+bool support_args_ok(const SupportCall& sc) {
+    return sc.out && sc.out->support && sc.thr > 0.0f && std::isfinite(sc.thr);
+}
+erp_status run_support(erp_ctx* c, const erp::BatchShape& sh, const erp_ransac_cfg* cfg,
+                       const erp_batch_outputs* out, const erp_pair_result* results,
+                       const SupportCall& sc, hipStream_t st) {
+    const bool lite = use_lite(cfg, out);
+    const erp::ConsensusLayout L = erp::consensus_layout(sh.n_pairs, sh.iters);
+    const erp::SupportScratch ss = erp::support_scratch(sh);
+    char* eb = erp::ctx_scratch<char>(c, erp::kSlotSupportE,
+                                      ss.ec64_bytes + ss.eimg_bytes + ss.xflag_bytes);
+    void* ub = erp::ctx_scratch<char>(c, erp::kSlotSupportU, ss.uimg_bytes);
+    int32_t* counts = sc.out->counts;
+    if (!counts) counts = erp::ctx_scratch<int32_t>(c, erp::kSlotSupportCounts, ss.counts_bytes);
+    if (!eb || !ub || !counts) return ERP_OUT_OF_MEMORY;
+    erp::SupportArgs a{};
+    a.results = results;
+    if (lite) {
+        a.evec = (const double*)c->gfin.p;
+        a.gram = (const double*)c->gram.p;
+        a.hl = erp::ws_at<float>(c->hlite.p, L.hlite.hl);
+    } else {
+        a.hyps = (out && out->hyps) ? out->hyps : (const erp_hypothesis*)c->hyps.p;
+    }
+    a.mcount = (const int32_t*)c->counts.p;
+    a.pts = (const double*)c->pts.p;
+    a.iters = sh.iters;
+    a.ipad = ss.ipad;
+    a.max_nq = sh.max_nq;
+    a.mpad = ss.mpad;
+    a.mfma = c->opt[ERP_OPT_SUPPORT_COUNT] != 0;
+    a.sample_frac = cfg->sample_frac;
+    a.valid_abs = cfg->valid_abs;
+    a.thr = (double)sc.thr;
+    erp::support_band(a.thr, a.mfma != 0, &a.thr_lo, &a.thr_hi);
+    a.ec64 = (double*)eb;
+    a.eimg = eb + ss.ec64_bytes;
+    a.xflag = (int32_t*)(eb + ss.ec64_bytes + ss.eimg_bytes);
+    a.uimg = ub;
+    a.counts = counts;
+    a.support = sc.out->support;
+    a.winners = sc.out->winners;
+    a.out_results = sc.out->results;
+    ERP_CK(erp::launch_support(a, sh.n_pairs, st));
+    return ERP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -834,6 +895,7 @@ erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value) {
         case ERP_OPT_DEBUG_STAGES: lo = -1; hi = 63; break;
         case ERP_OPT_SAMPLER_TIERS: lo = -1; hi = 4; break;
         case ERP_OPT_SAMPLER_SHARE: lo = -1; hi = 1; break;
+        case ERP_OPT_SUPPORT_COUNT: lo = -1; hi = 1; break;
         default: break;
     }
     if (value < lo || value > hi) return ERP_INVALID_ARG;
@@ -851,11 +913,12 @@ erp_status erp_ctx_get_option(erp_ctx* ctx, int32_t option, int32_t* value) {
 
 void erp_debug_set_alloc_pad(size_t bytes) { g_alloc_pad.store(bytes, std::memory_order_relaxed); }
 
-// erp_pair_batch_run (winners == nullptr) and erp_pair_batch_run_winners, which appends the
-// winner stage and always enqueues plainly
+// erp_pair_batch_run (winners == nullptr, sup == nullptr), erp_pair_batch_run_winners and
+// erp_pair_batch_run_support, which append their stage and always enqueue plainly
 static erp_status pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ratio,
                                  const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
-                                 erp_winner* winners, void* stream) {
+                                 erp_winner* winners, void* stream,
+                                 const SupportCall* sup = nullptr) {
     if (!ctx || !b || !out || !out->results || !cfg_ok(cfg)) return ERP_INVALID_ARG;
     if (b->n_pairs < 1 || b->dim != erp::kDim || b->max_nq < 0 || b->max_nt < 0 ||
         b->max_nq > 65535 || !b->desc_l || !b->desc_r || !b->kp_l || !b->kp_r || !b->off_l ||
@@ -864,7 +927,7 @@ static erp_status pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ra
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     CtxCall call(ctx, st);
-    if (winners && ctx->opt[ERP_OPT_DEBUG_STAGES] != -1) return ERP_INVALID_ARG;
+    if ((winners || sup) && ctx->opt[ERP_OPT_DEBUG_STAGES] != -1) return ERP_INVALID_ARG;
     const erp::BatchShape sh = make_shape(b->n_pairs, b->max_nq, b->max_nt, cfg->iters,
                                           cfg->sample_frac);
     if (!ensure_matcher(ctx, sh)) return ERP_OUT_OF_MEMORY;
@@ -886,13 +949,14 @@ static erp_status pair_batch_run(erp_ctx* ctx, const erp_pair_batch* b, float ra
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (st != nullptr) ERP_CK(hipStreamIsCapturing(st, &cap));
     if (!ctx->use_graphs || ctx->profiling || st == nullptr || ctx->opt[ERP_OPT_DEBUG_SNAP] ||
-        cap != hipStreamCaptureStatusNone || winners) {
+        cap != hipStreamCaptureStatusNone || winners || sup) {
         // (inside the caller's own capture the stream's event cannot order anything: the
         // caller's graph then owns the order of the calls that share the stream)
         ctx->rs_capture = cap != hipStreamCaptureStatusNone;
         es = batch_enqueue(ctx, b, ratio, cfg, out, sh, matches, st);
         ctx->rs_capture = false;
         if (es == ERP_OK && winners) es = run_winners(ctx, sh, cfg, out, out->results, winners, st);
+        if (es == ERP_OK && sup) es = run_support(ctx, sh, cfg, out, out->results, *sup, st);
         return es;
     }
     // graph replay: the same call (structs, buffers, scratch) as a captured one -> one launch.
@@ -950,6 +1014,14 @@ erp_status erp_pair_batch_run_winners(erp_ctx* ctx, const erp_pair_batch* b, flo
     return pair_batch_run(ctx, b, ratio, cfg, out, d_winners, stream);
 }
 
+erp_status erp_pair_batch_run_support(erp_ctx* ctx, const erp_pair_batch* b, float ratio,
+                                      const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
+                                      float thr, const erp_support_outputs* sup, void* stream) {
+    const SupportCall sc{thr, sup};
+    if (!support_args_ok(sc)) return ERP_INVALID_ARG;
+    return pair_batch_run(ctx, b, ratio, cfg, out, nullptr, stream, &sc);
+}
+
 erp_status erp_match_knn2_ratio(erp_ctx* ctx, const float* d_query, int32_t nq,
                                 const float* d_train, int32_t nt, int32_t dim, float ratio,
                                 erp_dmatch* d_out, int32_t* d_count, void* stream) {
@@ -1000,11 +1072,13 @@ erp_status erp_match_two_image(erp_ctx* ctx, const float* h_desc1, int32_t n1, c
     return ERP_OK;
 }
 
-// erp_eight_point_find_dev (d_winner == nullptr) and erp_eight_point_find_winner_dev
+// erp_eight_point_find_dev (d_winner == nullptr, sup == nullptr), erp_eight_point_find_winner_dev
+// and erp_eight_point_find_support_dev
 static erp_status find_dev(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f* d_kl,
                            const erp_point2f* d_kr, int32_t m, const erp_ransac_cfg* cfg,
                            erp_pair_result* d_result, erp_hypothesis* d_hyps,
-                           erp_winner* d_winner, void* stream) {
+                           erp_winner* d_winner, void* stream,
+                           const SupportCall* sup = nullptr) {
     if (!ctx || W <= 0 || H <= 0 || m < 0 || m > 65535 || !d_result || !cfg_ok(cfg) ||
         !sampler_m_ok(cfg, m))
         return ERP_INVALID_ARG;
@@ -1012,7 +1086,7 @@ static erp_status find_dev(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f
     ERP_CK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
     CtxCall call(ctx, st);
-    if (d_winner && ctx->opt[ERP_OPT_DEBUG_STAGES] != -1) return ERP_INVALID_ARG;
+    if ((d_winner || sup) && ctx->opt[ERP_OPT_DEBUG_STAGES] != -1) return ERP_INVALID_ARG;
     const erp::BatchShape sh = make_shape(1, m, m, cfg->iters, cfg->sample_frac);
     erp_batch_outputs out{};
     out.results = d_result;
@@ -1029,6 +1103,7 @@ static erp_status find_dev(erp_ctx* ctx, int32_t W, int32_t H, const erp_point2f
     }
     es = run_estimator(ctx, sh, cfg, &out, d_result, st);
     if (es == ERP_OK && d_winner) es = run_winners(ctx, sh, cfg, &out, d_result, d_winner, st);
+    if (es == ERP_OK && sup) es = run_support(ctx, sh, cfg, &out, d_result, *sup, st);
     return es;
 }
 
@@ -1046,6 +1121,17 @@ erp_status erp_eight_point_find_winner_dev(erp_ctx* ctx, int32_t W, int32_t H,
                                            erp_winner* d_winner, void* stream) {
     if (!d_winner) return ERP_INVALID_ARG;
     return find_dev(ctx, W, H, d_kl, d_kr, m, cfg, d_result, d_hyps, d_winner, stream);
+}
+
+erp_status erp_eight_point_find_support_dev(erp_ctx* ctx, int32_t W, int32_t H,
+                                            const erp_point2f* d_kl, const erp_point2f* d_kr,
+                                            int32_t m, const erp_ransac_cfg* cfg,
+                                            erp_pair_result* d_result, erp_hypothesis* d_hyps,
+                                            float thr, const erp_support_outputs* sup,
+                                            void* stream) {
+    const SupportCall sc{thr, sup};
+    if (!support_args_ok(sc)) return ERP_INVALID_ARG;
+    return find_dev(ctx, W, H, d_kl, d_kr, m, cfg, d_result, d_hyps, nullptr, stream, &sc);
 }
 
 erp_status erp_eight_point_hypotheses_dev(erp_ctx* ctx, int32_t W, int32_t H,
@@ -1206,6 +1292,50 @@ erp_status erp_eight_point_find_winner(erp_ctx* ctx, int32_t W, int32_t H,
                                        erp_winner* h_winner) {
     if (!h_winner || !cfg_ok(cfg)) return ERP_INVALID_ARG;
     return find_host(ctx, W, H, h_kl, h_kr, m, cfg, R_out, T_out, h_result, h_winner);
+}
+
+erp_status erp_eight_point_find_support(erp_ctx* ctx, int32_t W, int32_t H,
+                                        const erp_point2f* h_kl, const erp_point2f* h_kr,
+                                        int32_t m, const erp_ransac_cfg* cfg, float thr,
+                                        float R_out[3], float T_out[3], erp_pair_result* h_result,
+                                        erp_support* h_support, erp_winner* h_winner,
+                                        erp_pair_result* h_support_result, int32_t* h_counts) {
+    // (the stage's arguments first: a call that fails on them must not consume a rand stream)
+    if (!ctx || !h_support || !cfg_ok(cfg) || m < 0 || (m > 0 && (!h_kl || !h_kr)) ||
+        !(thr > 0.0f) || !std::isfinite(thr))
+        return ERP_INVALID_ARG;
+    // one lock across upload, find, the stage and download: the staging buffers are the context's
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    ERP_CK(hipSetDevice(ctx->device));
+    const erp::SupportStage L(cfg->iters);
+    erp_status s = erp::upload_keys(ctx, h_kl, h_kr, m);
+    if (s != ERP_OK) return s;
+    char* base = erp::ctx_scratch<char>(ctx, erp::kSlotHostStage, L.bytes);
+    if (!base) return ERP_OUT_OF_MEMORY;
+    erp_pair_result* d_res = (erp_pair_result*)(base + L.result);
+    erp_support_outputs so{};
+    so.support = (erp_support*)(base + L.support);
+    so.winners = (erp_winner*)(base + L.winner);
+    so.results = (erp_pair_result*)(base + L.support_result);
+    so.counts = (int32_t*)(base + L.counts);
+    const SupportCall sc{thr, &so};
+    s = find_dev(ctx, W, H, erp::keys_left(ctx), erp::keys_right(ctx), m, cfg, d_res, nullptr,
+                 nullptr, nullptr, &sc);
+    if (s != ERP_OK) return s;
+    erp_pair_result r, sr;
+    ERP_CK(hipMemcpy(&r, d_res, sizeof(r), hipMemcpyDeviceToHost));
+    ERP_CK(hipMemcpy(&sr, so.results, sizeof(sr), hipMemcpyDeviceToHost));
+    ERP_CK(hipMemcpy(h_support, so.support, sizeof(*h_support), hipMemcpyDeviceToHost));
+    if (h_winner) ERP_CK(hipMemcpy(h_winner, so.winners, sizeof(*h_winner), hipMemcpyDeviceToHost));
+    if (h_counts)
+        ERP_CK(hipMemcpy(h_counts, so.counts, (size_t)cfg->iters * 4, hipMemcpyDeviceToHost));
+    if (h_result) *h_result = r;
+    if (h_support_result) *h_support_result = sr;
+    if (R_out)
+        for (int k = 0; k < 3; k++) R_out[k] = sr.R[k];
+    if (T_out)
+        for (int k = 0; k < 3; k++) T_out[k] = sr.T[k];
+    return (erp_status)r.status;
 }
 
 erp_status erp_initial_guess(erp_ctx* ctx, const double* h_bl, const double* h_br, int32_t m,

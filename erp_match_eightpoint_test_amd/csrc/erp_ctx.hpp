@@ -52,6 +52,9 @@ enum CtxSlot {
     // guided.hip: the per-query (j0, e0, e1, |G_i|) records, the per-train-row 64-bit claim
     // words, and the train bearings with each pair's E'
     kSlotGuidedQuery, kSlotGuidedClaim, kSlotGuidedBearings,
+    // support.hip: every iteration's E' (fp64, the count kernel's operand image, the fp64-only
+    // flags), the matches' u = l (x) r image, and the counts when the caller keeps none
+    kSlotSupportE, kSlotSupportU, kSlotSupportCounts,
     kCtxSlotCount
 };
 
@@ -125,7 +128,8 @@ struct erp_ctx {
         0,   // DEBUG_SNAP
         -1,  // SAMPLER_TIERS: auto
         1,   // VERTICAL_SHARED: the batched vertical stage's shared-map kernel
-        -1};  // SAMPLER_SHARE: pairs of a launch with equal match counts share one replay
+        -1,  // SAMPLER_SHARE: pairs of a launch with equal match counts share one replay
+        -1};  // SUPPORT_COUNT: the support stage's count on bf16 MFMA (auto) or f32 VALU
     // debug (ERP_OPT_DEBUG_SNAP): lb, ub and the first-stage list counts right after the bounds
     // pass, fetched with erp_debug_snapshot
     DevBuf snap;

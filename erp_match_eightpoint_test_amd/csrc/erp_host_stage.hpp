@@ -1,6 +1,6 @@
 // erp_host_stage.hpp -- the device side of the one-pair host entry points behind find
-// (erp_eight_point_find_polished, erp_eight_point_find_posed, erp_match_guided): a bump layout
-// and the three layouts built on it, all in the context's one kSlotHostStage.  Host only, plain
+// (erp_eight_point_find_polished, erp_eight_point_find_posed, erp_match_guided,
+// erp_eight_point_find_support): a bump layout and the four layouts built on it, all in the context's one kSlotHostStage.  Host only, plain
 // C++17, no HIP types: a stand-alone g++ program checks it (tests/cpp/host_stage_check.cpp).
 // Precondition: the slot's base address is at least 16-byte aligned (hipMalloc gives 256), so an
 // offset's alignment is the address's.
@@ -68,6 +68,19 @@ struct GuidedStage {
         kp2 = l.add((size_t)n2 * sizeof(erp_point2f), 8);
         wh = l.add(2 * sizeof(int32_t), 4);
         count = l.add(sizeof(int32_t), 4);
+        bytes = l.total();
+    }
+};
+
+struct SupportStage {
+    size_t result, support, winner, support_result, counts, bytes;
+    explicit SupportStage(int32_t iters) {
+        StageLayout l;
+        result = l.add(sizeof(erp_pair_result), 8);
+        support = l.add(sizeof(erp_support), 4);
+        winner = l.add(sizeof(erp_winner), 8);
+        support_result = l.add(sizeof(erp_pair_result), 8);
+        counts = l.add((size_t)iters * sizeof(int32_t), 4);
         bytes = l.total();
     }
 };

@@ -217,6 +217,39 @@ struct WinnerArgs {
     erp_winner* out;                  // [P]
 };
 hipError_t launch_winner(const WinnerArgs& a, int n_pairs, hipStream_t st);
+// The support stage (support.hip; include/erp_match.h "support-scored winner"), after the
+// consensus: every iteration's inlier count under thr, the best-supported scored iteration per
+// pair and its records.  It reads what the run left (the records, or evec / gram / hl of the lite
+// route; counts, pts) and writes only its own scratch and the caller's outputs.  Four launches.
+struct SupportScratch {               // support_scratch(sh): the padded extents and the parts
+    int ipad, mpad;                   // iterations / matches rounded up to the kernels' tiles
+    size_t ec64_bytes, eimg_bytes, xflag_bytes, uimg_bytes, counts_bytes;
+};
+struct SupportArgs {
+    const erp_pair_result* results;   // [P] the run's records
+    const erp_hypothesis* hyps;       // [P][iters], or null: the lite route
+    const double* evec;               // [P][9][iters] (lite)
+    const double* gram;               // [P][36][iters] (lite)
+    const float* hl;                  // [P][9][iters] (lite)
+    const int32_t* mcount;            // [P] M
+    const double* pts;                // [P][max_nq + 1][6]
+    int iters, ipad, max_nq, mpad;
+    int mfma;                         // the count's fast evaluation: 1 bf16 MFMA, 0 f32 VALU
+    double sample_frac, valid_abs, thr;
+    float thr_lo, thr_hi;             // support_band(thr, mfma)
+    double* ec64;                     // scratch [P][iters][9]: E' (the exact path)
+    void* eimg;                       // scratch [P][ipad] x 64 B: E' as the count's operand
+    int32_t* xflag;                   // scratch [P][ipad]: iterations counted in fp64 only (MFMA)
+    void* uimg;                       // scratch [P][mpad] x 64 B: u = l (x) r as the operand
+    int32_t* counts;                  // [P][iters] (the caller's, or scratch)
+    erp_support* support;             // [P]
+    erp_winner* winners;              // [P] or null
+    erp_pair_result* out_results;     // [P] or null
+};
+SupportScratch support_scratch(const BatchShape& sh);
+// the f32 constants of the count's band: |x| < lo is an inlier, |x| >= hi is not
+void support_band(double thr, bool mfma, float* lo, float* hi);
+hipError_t launch_support(const SupportArgs& a, int n_pairs, hipStream_t st);
 hipError_t launch_gram_all(const double* pts, int32_t m, double* gram, hipStream_t st);
 hipError_t launch_consensus_input(const float* rvec, const float* tvec, int K, int stride, float* rv,
                                   float* tv, int32_t* kcount, float* dscale, int32_t* flags,

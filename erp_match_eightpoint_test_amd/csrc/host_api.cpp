@@ -126,6 +126,19 @@ void eight_point::find_winner(int W, int H, std::vector<KeyPoint>& kl, std::vect
     check((erp_status)winner.status, "find_winner: winner record");
 }
 
+void eight_point::find_support(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
+                               Vec3f& R, Vec3f& T, int match_size, float thr, erp_support& support,
+                               erp_winner& winner, std::vector<int32_t>* counts) {
+    std::vector<erp_point2f> a, b;
+    keys(kl, kr, match_size, "find_support: match_size", a, b);
+    if (counts) counts->assign((size_t)(cfg.iters > 0 ? cfg.iters : 0), 0);
+    check(erp_eight_point_find_support(ctx_, W, H, a.data(), b.data(), match_size, &cfg, thr, R.val,
+                                       T.val, &last_, &support, &winner, nullptr,
+                                       counts && !counts->empty() ? counts->data() : nullptr),
+          "find_support");
+    check((erp_status)support.status, "find_support: support record");
+}
+
 void eight_point::find_polished(int W, int H, std::vector<KeyPoint>& kl, std::vector<KeyPoint>& kr,
                                 Vec3f& R, Vec3f& T, int match_size, float thr, int rounds,
                                 std::vector<uint8_t>* inlier_mask) {

@@ -51,6 +51,16 @@ public:
     void find_winner(int im_width, int im_height, std::vector<KeyPoint>& key_left,
                      std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out,
                      int match_size, erp_winner& winner);
+    // find plus the support stage (erp_match.h "support-scored winner"; no reference
+    // counterpart): R_vec_out / T_vec_out are the rotation and T of the scored iteration most
+    // matches agree with under |l^T E' r| < thr, winner.E its solved 9-vector; last_result() is
+    // find's own record (the consensus winner).  counts (optional) gets every iteration's
+    // inlier count.  Pays with minimal samples (cfg.sample_frac for ~10 rows), not at the
+    // reference's 0.25.  Draws from the stream as find does.
+    void find_support(int im_width, int im_height, std::vector<KeyPoint>& key_left,
+                      std::vector<KeyPoint>& key_right, Vec3f& R_vec_out, Vec3f& T_vec_out,
+                      int match_size, float thr, erp_support& support, erp_winner& winner,
+                      std::vector<int32_t>* counts = nullptr);
     // src/eight_point.hpp:15-19
     void eight_point_estimation(int im_width, int im_height, std::vector<Point3d>& key_point_left_rect,
                                 std::vector<Point3d>& key_point_right_rect, Vec3f& R1_vec,

@@ -327,6 +327,10 @@ erp_status erp_ctx_set_graphs(erp_ctx* ctx, int32_t enable);
                           (erp_vertical_rotate_batch_dev, erp_rectify_batch_dev): 1 (default)
                           one shared-map launch over every image, 0 ROT90 jobs of the per-image
                           remap kernel, 8 per launch
+   ERP_OPT_SUPPORT_COUNT  the support stage's per-iteration count (erp_pair_batch_run_support): -1
+                          auto = 1 the bf16 MFMA product with an exact fp64 recheck of its band,
+                          0 the f32 VALU chain with its (narrower) band; the counts are exact
+                          either way
    ERP_OPT_DEBUG_STAGES   debug: bit mask of the stage groups erp_pair_batch_run enqueues (1
                           matcher + gather, 2 jump polynomials + windows, 4 sampler, 8 Gram, 32
                           eigen + estimate, 16 consensus); -1 (default) all.  A skipped group
@@ -351,7 +355,8 @@ typedef enum erp_ctx_option {
     ERP_OPT_SAMPLER_TIERS = 13,
     ERP_OPT_VERTICAL_SHARED = 14,
     ERP_OPT_SAMPLER_SHARE = 15,
-    ERP_OPT_COUNT = 16
+    ERP_OPT_SUPPORT_COUNT = 16,
+    ERP_OPT_COUNT = 17
 } erp_ctx_option;
 /* ERP_INVALID_ARG for an unknown option or a value outside its range */
 erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value);
@@ -620,6 +625,85 @@ erp_status erp_polish_winners_dev(erp_ctx* ctx, const erp_polish_inputs* in,
                                   const erp_winner* d_winners, double valid_abs, float thr,
                                   int32_t rounds, erp_polish_result* d_out,
                                   erp_polish_round* d_rounds, uint8_t* d_mask, void* stream);
+
+/* ---- support-scored winner: the best-supported hypothesis per pair ----
+   No reference counterpart; opt-in.  find returns the consensus winner, the rotation nearest
+   the trimmed mean of all hypotheses (src/eight_point.cpp:129-149): faithful to the reference,
+   and not what a RANSAC user expects, which is the hypothesis most matches agree with.  The
+   support stage runs behind the consensus, on the same context, and reads the run's scratch as
+   the winner stage does -- on the records route (out->hyps given, or cfg->inlier_thr > 0) and on
+   the lite route alike; cfg->inlier_thr may stay 0.  Per pair with result status ERP_OK, a
+   threshold thr > 0 (float, widened to double) and the call's cfg (all exact):
+   1. e_h = the solved 9-vector of iteration h, byte for byte erp_hypothesis.E of the same run
+      with records; E'_h = E_mat_correct(e_h) (src/eight_point.cpp:45-50).
+   2. count_h = #{ i < M : |l_i^T E'_h r_i| < thr }, fp64 in the fixed order given at
+      erp_ransac_cfg.inlier_thr: for every h exactly what cfg->inlier_thr = thr writes into
+      hyps[h].inliers.  Iterations with no valid rotation get a count too.
+   3. Scored iterations are those with R1 or R2 valid.  iter = the scored iteration with the
+      largest count, the smallest h on ties.  which = its valid rotation; when both are valid, the
+      one nearer to the result record's R by the consensus' float distance (sqrtf of the float
+      squared differences, src/eight_point.cpp:138-139), R1 on a tie: the polish's rule.
+   4. row = the index (iter, which) has in push order (R1 then R2 per iteration, :113-126).
+   5. consensus_iter = the iteration that pushed row min_idx; consensus_inliers = its count.
+   Before it writes, the stage re-runs the estimate on e_iter and compares the validity flags
+   and, byte for byte, the chosen rotation and T with what the run stored for that iteration: a
+   mismatch (or a min_idx that names no row) gives the pair ERP_INTERNAL and zeros, never a
+   plausible record.  A pair whose result status is not ERP_OK gets that status and zeros.
+   When it pays: with minimal samples (cfg->sample_frac chosen for s ~ 10 rows) the best-supported
+   hypothesis recovers the pose where the consensus winner is degrees off; with the reference's
+   25 % samples every sample of a contaminated list is contaminated and the support winner is
+   no better, often worse (INTEGRATION.md has the table).  The stage allocates nothing inside the
+   call's enqueue, synchronises nothing, uses no atomics and draws no rand(). */
+typedef struct erp_support {     /* 32 bytes */
+    int32_t status;              /* the pair's erp_status; not ERP_OK: the rest is zero */
+    int32_t iter;                /* the best-supported scored iteration */
+    int32_t which;               /* 0: its R1, 1: its R2 (rule 3) */
+    int32_t inliers;             /* count_iter */
+    int32_t scored;              /* iterations with a valid rotation */
+    int32_t consensus_iter;      /* the iteration that pushed row min_idx */
+    int32_t consensus_inliers;   /* its count */
+    int32_t row;                 /* (iter, which) in R_vec_arr order */
+} erp_support;
+/* device outputs of the support stage (caller-owned; NULL = not needed) */
+typedef struct erp_support_outputs {
+    erp_support* support;        /* [n_pairs] (required) */
+    erp_winner* winners;         /* [n_pairs] {status, iter, which, sample_n, E = e_iter}: what
+                                    erp_polish_winners_dev, erp_pose_select_dev,
+                                    erp_match_guided_dev and erp_epipolar_draw_dev take */
+    erp_pair_result* results;    /* [n_pairs] the run's records with R and T replaced by that
+                                    iteration's chosen rotation and its T (the f32 values the
+                                    estimate wrote) and min_idx by row; every other field is
+                                    copied: min_dist, near_ties, survivors and binned_rows still
+                                    describe the consensus.  A pair that is not ERP_OK: a copy */
+    int32_t* counts;             /* [n_pairs][iters] count_h; rows of pairs that are not ERP_OK
+                                    are zeros */
+} erp_support_outputs;
+/* erp_pair_batch_run followed by the support stage; results and every other output of `out` are
+   erp_pair_batch_run's.  A consuming call on a rand stream exactly as erp_pair_batch_run is.
+   With erp_ctx_set_graphs on, this call still enqueues plainly; the stage is not timed by
+   erp_ctx_set_profiling.  ERP_INVALID_ARG when thr <= 0 or not finite, sup or sup->support is
+   NULL, or ERP_OPT_DEBUG_STAGES is not -1 (a skipped stage group would leave another call's
+   scratch under the stage). */
+erp_status erp_pair_batch_run_support(erp_ctx* ctx, const erp_pair_batch* batch, float ratio,
+                                      const erp_ransac_cfg* cfg, const erp_batch_outputs* out,
+                                      float thr, const erp_support_outputs* sup, void* stream);
+/* erp_eight_point_find_dev followed by the support stage (n_pairs = 1): d_hyps may be NULL (the
+   lite route).  Arguments as above. */
+erp_status erp_eight_point_find_support_dev(erp_ctx* ctx, int32_t W, int32_t H,
+                                            const erp_point2f* d_kl, const erp_point2f* d_kr,
+                                            int32_t m, const erp_ransac_cfg* cfg,
+                                            erp_pair_result* d_result, erp_hypothesis* d_hyps,
+                                            float thr, const erp_support_outputs* sup,
+                                            void* stream);
+/* host pointers, synchronous: erp_eight_point_find plus the support stage.  h_support is
+   required; R_out, T_out (the support winner's rotation and T), h_result (find's own record),
+   h_winner, h_support_result and h_counts [cfg->iters] may be NULL.  Returns the find's status. */
+erp_status erp_eight_point_find_support(erp_ctx* ctx, int32_t W, int32_t H,
+                                        const erp_point2f* h_kl, const erp_point2f* h_kr,
+                                        int32_t m, const erp_ransac_cfg* cfg, float thr,
+                                        float R_out[3], float T_out[3], erp_pair_result* h_result,
+                                        erp_support* h_support, erp_winner* h_winner,
+                                        erp_pair_result* h_support_result, int32_t* h_counts);
 
 /* ---- pose selection: the cheirality vote over (R1 | R2) x (+t | -t), with depths ----
    No reference counterpart; opt-in.  decomposeEssentialMat gives two rotations and a translation
