@@ -14,6 +14,8 @@ Host-side mirror of the reference's hot-path classes (Kitsunetic/ERP_match_eight
   ``spherical_surf.do_all_batch``, ``run_sweep`` for the drivers' rotation sweeps: one left
   image against a right base image under a list of poses, with the surf match error,
   ``rectify_images`` on to automatic's rectified and vertical views of every pair).
+* ``stereo`` -- dense disparity and depth on those vertical views (census + 4-path SGM; no
+  reference counterpart, include/erp_match.h "dense stereo on row-rectified views").
 
 Every call goes through the C ABI of ``lib/liberp_match.so`` (include/erp_match.h); there is
 no CPU fallback.  Arrays are numpy (host, synchronous) or torch CUDA tensors (device,
@@ -35,7 +37,7 @@ __all__ = ["feature_matcher", "eight_point", "erp_rotation", "spherical_surf", "
            "default_cfg", "DMATCH_DTYPE", "HYP_DTYPE", "RESULT_DTYPE", "POLISH_DTYPE",
            "POLISH_ROUND_DTYPE", "WINNER_DTYPE", "results_to_numpy", "hyps_to_numpy",
            "polish_to_numpy", "polish_rounds_to_numpy", "winners_to_numpy", "sweep_relative_rotation", "synth", "capi",
-           "POSE_DTYPE", "pose_to_numpy", "SUPPORT_DTYPE", "support_to_numpy"]
+           "POSE_DTYPE", "pose_to_numpy", "SUPPORT_DTYPE", "support_to_numpy", "stereo"]
 
 
 def _np_ptr(a: np.ndarray):
@@ -874,6 +876,61 @@ def _image_batch_dev(lefts, rights):
     if lefts.shape[1] < 4 or lefts.shape[2] < 1:
         raise ValueError("images need H >= 4 and W >= 1")
     return lefts, rights
+
+
+_stereo_ctx: dict = {}
+
+
+class stereo:  # noqa: N801  (a namespace, as the reference-named classes above)
+    """Dense disparity on row-rectified views (include/erp_match.h "dense stereo on
+    row-rectified views"): census + 4-path SGM, sub-pixel winner, left-right check, optional
+    depth.  Images are contiguous CUDA uint8 tensors [rows, cols] (gray), [rows, cols, C] or
+    [P, rows, cols, C] with C = 1 or 3 (BGR); the outputs have the images' shape without C."""
+
+    @staticmethod
+    def disparity(left, right, *, d_min: int = 0, n_disp: int = 64, p1: int = 8, p2: int = 64,
+                  lr_max: int = 1, wrap_rows: int = 0, depth: bool = False, ctx=None):
+        """erp_stereo_rows_dev -> disp16 (int16, the left image's disparity in 1/16 pixel,
+        capi.STEREO_INVALID where rejected), or (disp16, depth float32) with ``depth``.
+        Asynchronous on torch's current stream.  ctx=None: one context per device, kept."""
+        import torch
+        for t in (left, right):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8
+                    and t.is_contiguous() and 2 <= t.dim() <= 4
+                    and (t.dim() == 2 or t.shape[-1] in (1, 3))):
+                raise ValueError("views are contiguous CUDA uint8 tensors [rows, cols], "
+                                 "[rows, cols, C] or [P, rows, cols, C], C = 1 or 3")
+        if left.shape != right.shape or left.device != right.device:
+            raise ValueError("left and right differ in shape or device")
+        dev = left.device
+        if ctx is None:
+            ctx = _stereo_ctx.get(dev.index)
+            if ctx is None:
+                ctx = _stereo_ctx[dev.index] = Context(dev.index)
+        elif dev.index != ctx.device:
+            raise ValueError(f"views must be on the context's device cuda:{ctx.device}")
+        shape = tuple(left.shape) if left.dim() == 2 else tuple(left.shape[:-1])
+        n = shape[0] if left.dim() == 4 else 1
+        rows, cols = shape[-2:]
+        par = capi.StereoParams(int(d_min), int(n_disp), int(p1), int(p2), int(lr_max),
+                                int(wrap_rows), 1 if left.dim() == 2 else left.shape[-1])
+        disp16 = torch.empty(shape, dtype=torch.int16, device=dev)
+        z = torch.empty(shape, dtype=torch.float32, device=dev) if depth else None
+        ptr = lambda t: t.data_ptr() if t is not None and n else None  # noqa: E731
+        check(ctx.L.erp_stereo_rows_dev(ctx.h, ptr(left), ptr(right), n, rows, cols,
+                                        C.byref(par), ptr(disp16), ptr(z),
+                                        torch.cuda.current_stream(dev).cuda_stream),
+              "erp_stereo_rows_dev")
+        return (disp16, z) if depth else disp16
+
+    @staticmethod
+    def vertical(left_vertical, right_vertical, **kw):
+        """disparity on the vertical views of erp_rotation.rectify_batch /
+        PairBatchRunner.rectify_images ([P, W, H, 3]: W rows of H columns, the row index being
+        longitude): wrap_rows = 1."""
+        if "wrap_rows" in kw:
+            raise ValueError("vertical views wrap their rows; use disparity for wrap_rows = 0")
+        return stereo.disparity(left_vertical, right_vertical, wrap_rows=1, **kw)
 
 
 def _rot_mats_host(rot_mats) -> np.ndarray:

@@ -21,7 +21,7 @@ ARCH = os.environ.get("ERP_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["kernels.hip", "matcher.hip", "capi.hip", "remap.hip", "remap_api.hip", "surf.hip", "surf_api.hip", "viz.hip",
            "image_batch.hip", "rand_stream.hip", "sweep.hip", "polish.hip", "winner.hip", "pose.hip",
-           "guided.hip", "support.hip",
+           "guided.hip", "support.hip", "stereo.hip",
            "host_api.cpp"]
 HEADERS = ["erp_device.hpp", "erp_kernels.hpp", "erp_consensus_ws.hpp", "erp_remap.hpp", "erp_surf.hpp",
            "erp_launch.hpp", "erp_jump_poly.hpp", "erp_image_batch.hpp", "erp_ctx.hpp", "erp_winner.hpp",
@@ -123,6 +123,7 @@ DRIVERS = {
     "pose": "pose_driver",           # erp::eight_point::find_posed
     "guided": "guided_driver",       # erp::feature_matcher::match_guided
     "support": "support_driver",     # erp::eight_point::find_support
+    "stereo": "stereo_driver",       # erp_stereo_rows_dev, the C ABI from C++
 }
 
 

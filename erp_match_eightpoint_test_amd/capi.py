@@ -205,7 +205,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_eight_point_find_winner_dev", "erp_eight_point_find_winner",
             "erp_polish_winners_dev", "erp_pose_select_dev", "erp_eight_point_find_posed",
             "erp_match_guided_dev", "erp_match_guided", "erp_pair_batch_run_support",
-            "erp_eight_point_find_support_dev", "erp_eight_point_find_support"]
+            "erp_eight_point_find_support_dev", "erp_eight_point_find_support",
+            "erp_stereo_params_default", "erp_stereo_rows_dev"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -215,7 +216,7 @@ OPTIONS = {"small_batch": 0, "sampler_lat": 1, "sampler_split": 2, "gram_tiles":
            "zoom_levels": 4, "small_zoom": 5, "lip2": 6, "lipg": 7, "refine_hint": 8,
            "flat_refs": 9, "bound_ratio": 10, "debug_stages": 11, "debug_snap": 12,
            "sampler_tiers": 13, "vertical_shared": 14, "sampler_share": 15,
-           "support_count": 16}
+           "support_count": 16, "stereo_chunk_mb": 17}
 MATCHER_MFMA_FILTER = 0  # erp_matcher_method
 MATCHER_VALU_EXACT = 1
 
@@ -238,6 +239,14 @@ class ImageBatchInfo(C.Structure):
 
 
 assert C.sizeof(PackedPairs) == 88 and C.sizeof(ImageBatchInfo) == 40
+
+
+STEREO_INVALID = -32768  # ERP_STEREO_INVALID
+
+
+class StereoParams(C.Structure):
+    _fields_ = [("d_min", C.c_int32), ("n_disp", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32),
+                ("lr_max", C.c_int32), ("wrap_rows", C.c_int32), ("channels", C.c_int32)]
 
 
 class RectifyOutputs(C.Structure):
@@ -407,6 +416,10 @@ def load(build_if_missing: bool = False):
                                        C.POINTER(GuidedOutputs), P]
     L.erp_match_guided.argtypes = [P, P, C.c_int32, P, C.c_int32, P, P, C.c_int32, C.c_int32, P,
                                    C.POINTER(GuidedCfg), P, P]
+    L.erp_stereo_params_default.argtypes = [C.POINTER(StereoParams)]
+    L.erp_stereo_params_default.restype = None
+    L.erp_stereo_rows_dev.argtypes = [P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                      C.POINTER(StereoParams), P, P, P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]

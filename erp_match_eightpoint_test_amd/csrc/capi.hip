@@ -896,6 +896,7 @@ erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value) {
         case ERP_OPT_SAMPLER_TIERS: lo = -1; hi = 4; break;
         case ERP_OPT_SAMPLER_SHARE: lo = -1; hi = 1; break;
         case ERP_OPT_SUPPORT_COUNT: lo = -1; hi = 1; break;
+        case ERP_OPT_STEREO_CHUNK_MB: lo = 0; hi = 1 << 20; break;
         default: break;
     }
     if (value < lo || value > hi) return ERP_INVALID_ARG;

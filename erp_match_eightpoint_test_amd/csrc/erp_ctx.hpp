@@ -55,6 +55,9 @@ enum CtxSlot {
     // support.hip: every iteration's E' (fp64, the count kernel's operand image, the fp64-only
     // flags), the matches' u = l (x) r image, and the counts when the caller keeps none
     kSlotSupportE, kSlotSupportU, kSlotSupportCounts,
+    // stereo.hip: a chunk's census words (left then right), its S volume, and its winners
+    // (d* then dR)
+    kSlotStereoCensus, kSlotStereoVolume, kSlotStereoWinners,
     kCtxSlotCount
 };
 
@@ -129,7 +132,8 @@ struct erp_ctx {
         -1,  // SAMPLER_TIERS: auto
         1,   // VERTICAL_SHARED: the batched vertical stage's shared-map kernel
         -1,  // SAMPLER_SHARE: pairs of a launch with equal match counts share one replay
-        -1};  // SUPPORT_COUNT: the support stage's count on bf16 MFMA (auto) or f32 VALU
+        -1,  // SUPPORT_COUNT: the support stage's count on bf16 MFMA (auto) or f32 VALU
+        1024};  // STEREO_CHUNK_MB: the S volume a chunk of stereo pairs may take (stereo.hip)
     // debug (ERP_OPT_DEBUG_SNAP): lb, ub and the first-stage list counts right after the bounds
     // pass, fetched with erp_debug_snapshot
     DevBuf snap;

@@ -331,6 +331,9 @@ erp_status erp_ctx_set_graphs(erp_ctx* ctx, int32_t enable);
                           auto = 1 the bf16 MFMA product with an exact fp64 recheck of its band,
                           0 the f32 VALU chain with its (narrower) band; the counts are exact
                           either way
+   ERP_OPT_STEREO_CHUNK_MB  erp_stereo_rows_dev: the MiB of S volume a chunk of pairs may take
+                          in the scratch (0..1048576, default 1024; a chunk is never smaller
+                          than one pair, so 0 runs the pairs one by one)
    ERP_OPT_DEBUG_STAGES   debug: bit mask of the stage groups erp_pair_batch_run enqueues (1
                           matcher + gather, 2 jump polynomials + windows, 4 sampler, 8 Gram, 32
                           eigen + estimate, 16 consensus); -1 (default) all.  A skipped group
@@ -356,7 +359,8 @@ typedef enum erp_ctx_option {
     ERP_OPT_VERTICAL_SHARED = 14,
     ERP_OPT_SAMPLER_SHARE = 15,
     ERP_OPT_SUPPORT_COUNT = 16,
-    ERP_OPT_COUNT = 17
+    ERP_OPT_STEREO_CHUNK_MB = 17,
+    ERP_OPT_COUNT = 18
 } erp_ctx_option;
 /* ERP_INVALID_ARG for an unknown option or a value outside its range */
 erp_status erp_ctx_set_option(erp_ctx* ctx, int32_t option, int32_t value);
@@ -975,6 +979,78 @@ erp_status erp_rectify_results_dev(erp_ctx* ctx, const uint8_t* d_left, const ui
                                    int32_t n_pairs, int32_t W, int32_t H,
                                    const erp_pair_result* d_results, int32_t fill,
                                    const erp_rectify_outputs* outputs, void* stream);
+
+/* ---- dense stereo on row-rectified views: census + 4-path SGM (no reference counterpart) ----
+   The vertical views of erp_rectify_outputs are what this is for: rectify turns the baseline
+   onto (0, -1, 0), the 89.999-degree turn about x puts both epipoles on the poles and the
+   90-degree rotation makes every meridian -- one epipolar half-plane -- a row, so that a scene
+   point lies on the same row of both [W rows][H columns] views and stereo is a 1-D search
+   along rows (rows = W, cols = H, wrap_rows = 1: the row index is longitude and periodic).
+   The call works on any pair of row-rectified 8-bit images.
+
+   Rules.  Everything is integer arithmetic except the depth, so a caller can restate the
+   output bit for bit (tests/stereo_ref.py does).  Pixel (y, x) of both images belongs to row y;
+   D = n_disp.
+   1. Gray.  channels == 3: (b*1868 + g*9617 + r*4899 + 8192) >> 14 on the bytes b, g, r in that
+      order (SURF's gray conversion); channels == 1: the byte.
+   2. Census.  Window 9 wide, 7 tall; its neighbours in row-major order, dy = -3..3, dx = -4..4,
+      the centre skipped: 62 bits.  Bit k (LSB first) = gray(neighbour k) < gray(centre).
+      Columns clamp to [0, cols-1].  Rows wrap modulo `rows` (any rows >= 1, also below 7) when
+      wrap_rows is set and clamp to [0, rows-1] otherwise.
+   3. Cost.  For d in [0, D): xr = x - d_min - d; c(y,x,d) = popcount(cenL(y,x) ^ cenR(y,xr))
+      when 0 <= xr < cols, else 63.
+   4. Aggregation.  Four paths r: left to right, right to left, top to bottom, bottom to top;
+      none wraps.  The first pixel of a path has L_r = c.  After it, with q the previous pixel on
+      the path and m = min_k L_r(q,k),
+        L_r(p,d) = c(p,d) + min(L_r(q,d), L_r(q,d-1) + p1, L_r(q,d+1) + p1, m + p2) - m,
+      a neighbour d-1 or d+1 outside [0, D) left out.  S = the sum of the four L_r, uint16
+      (L_r <= 63 + p2, so S <= 1272).
+   5. Winner and sub-pixel.  d* = the first argmin over d of S(y,x,.).  a = S[d*-1],
+      b = S[d*+1], c = S[d*], den = a + b - 2c.  off = 0 when d* is 0 or D-1 or den <= 0, else
+      off = floor(((a - b)*16 + den) / (2*den)) (floor division on signed integers).
+      disp16 = 16*(d_min + d*) + off.
+   6. Right disparity and left-right check.  dR(y,xr) = the first argmin over d of
+      S(y, xr + d_min + d, d) over the d whose column xr + d_min + d is in [0, cols).  Pixel
+      (y,x) is invalid (ERP_STEREO_INVALID) when its xr = x - d_min - d* is outside [0, cols),
+      or when lr_max >= 0 and abs(d* - dR(y,xr)) > lr_max.
+   7. Depth (optional), the left camera's, in units of |t|, meant for vertical views, where a
+      row runs from pole to pole; the pixel-to-angle rule is the reference's pi * i / H
+      (src/erp_rotation.cpp:68; no half-pixel offset).  thL = pi*x/cols,
+      thR = pi*(x - disp16/16.0)/cols, depth = sin(thR) / abs(sin(thL - thR)), evaluated in
+      fp64 in exactly that order (M_PI * x, then / cols) and stored as float: the sine rule on
+      the triangle (left centre, right centre, point), whose angle at the point is
+      abs(thL - thR) and whose interior angle at the right centre has sine sin(thR) whichever
+      pole the baseline points to.  +inf where disp16 == 0, NaN where the
+      pixel is invalid.
+
+   p1 = 8 and p2 = 64 are starting values: nobody has tuned them on real views yet. */
+#define ERP_STEREO_INVALID (-32768)
+typedef struct erp_stereo_params {
+    int32_t d_min;      /* first disparity searched (signed); default 0 */
+    int32_t n_disp;     /* D: a multiple of 16 in 16..256, abs(d_min) + D <= 2047; default 64 */
+    int32_t p1;         /* 0 <= p1 <= p2 <= 255; default 8 */
+    int32_t p2;         /* default 64 */
+    int32_t lr_max;     /* whole pixels; -1 disables the left-right check; default 1 */
+    int32_t wrap_rows;  /* 0 or 1; 1 for vertical views; default 0 */
+    int32_t channels;   /* 1 or 3; default 3 */
+} erp_stereo_params;
+void erp_stereo_params_default(erp_stereo_params* p);
+/* d_left / d_right [n_pairs][rows][cols][channels] uint8 -> d_disp16 [n_pairs][rows][cols]
+   int16, the left image's disparity in 1/16 pixel (ERP_STEREO_INVALID where rejected), and
+   d_depth [n_pairs][rows][cols] float (may be NULL).  Device pointers; asynchronous on
+   `stream`; deterministic (no atomics, no floating-point sums).  The census words, the S
+   volume (rows * cols * D * 2 bytes per pair) and the winners live in the context's grow-only
+   scratch, sized for a chunk of pairs at a time: as many pairs as fit ERP_OPT_STEREO_CHUNK_MB
+   of S volume (default 1024 MiB), at least one; the chunks run one after the other on
+   `stream` and every chunk size gives the same bytes.
+   n_pairs == 0: ERP_OK, nothing is done.  Before any launch, ERP_INVALID_ARG for: a NULL ctx,
+   params, d_left, d_right or d_disp16, n_pairs < 0, rows < 1, cols < 1, rows * cols > 2^30,
+   or a parameter outside the rules of the table above. */
+erp_status erp_stereo_rows_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                               int32_t n_pairs, int32_t rows, int32_t cols,
+                               const erp_stereo_params* params, int16_t* d_disp16,
+                               float* d_depth, void* stream);
+
 /* ---- SURF: feature_matcher::detect_key_point + comput_descriptor
    (src/feature_matcher.cpp:26-40) with xfeatures2d::SURF::create() defaults ---- */
 typedef struct erp_keypoint {   /* cv::KeyPoint layout */
