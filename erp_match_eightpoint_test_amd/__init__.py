@@ -14,7 +14,7 @@ Host-side mirror of the reference's hot-path classes (Kitsunetic/ERP_match_eight
   ``spherical_surf.do_all_batch``, ``run_sweep`` for the drivers' rotation sweeps: one left
   image against a right base image under a list of poses, with the surf match error,
   ``rectify_images`` on to automatic's rectified and vertical views of every pair).
-* ``stereo`` -- dense disparity and depth on those vertical views (census + 4-path SGM; no
+* ``stereo`` -- dense disparity and depth on those vertical views (census + 4- or 8-path SGM; no
   reference counterpart, include/erp_match.h "dense stereo on row-rectified views").
 
 Every call goes through the C ABI of ``lib/liberp_match.so`` (include/erp_match.h); there is
@@ -883,15 +883,19 @@ _stereo_ctx: dict = {}
 
 class stereo:  # noqa: N801  (a namespace, as the reference-named classes above)
     """Dense disparity on row-rectified views (include/erp_match.h "dense stereo on
-    row-rectified views"): census + 4-path SGM, sub-pixel winner, left-right check, optional
+    row-rectified views"): census + 4- or 8-path SGM, sub-pixel winner, left-right check, optional
     depth.  Images are contiguous CUDA uint8 tensors [rows, cols] (gray), [rows, cols, C] or
     [P, rows, cols, C] with C = 1 or 3 (BGR); the outputs have the images' shape without C."""
 
     @staticmethod
     def disparity(left, right, *, d_min: int = 0, n_disp: int = 64, p1: int = 8, p2: int = 64,
-                  lr_max: int = 1, wrap_rows: int = 0, depth: bool = False, ctx=None):
+                  lr_max: int = 1, wrap_rows: int = 0, n_paths: int = 4, uniqueness: int = 0,
+                  depth: bool = False, ctx=None):
         """erp_stereo_rows_dev -> disp16 (int16, the left image's disparity in 1/16 pixel,
         capi.STEREO_INVALID where rejected), or (disp16, depth float32) with ``depth``.
+        ``n_paths`` = 8 adds the four diagonal paths (rule 4b), ``uniqueness`` = 1..99 the
+        uniqueness test in percent (rule 6b); either goes through erp_stereo_rows_ex_dev, the
+        defaults through the call above.
         Asynchronous on torch's current stream.  ctx=None: one context per device, kept."""
         import torch
         for t in (left, right):
@@ -917,17 +921,21 @@ class stereo:  # noqa: N801  (a namespace, as the reference-named classes above)
         disp16 = torch.empty(shape, dtype=torch.int16, device=dev)
         z = torch.empty(shape, dtype=torch.float32, device=dev) if depth else None
         ptr = lambda t: t.data_ptr() if t is not None and n else None  # noqa: E731
-        check(ctx.L.erp_stereo_rows_dev(ctx.h, ptr(left), ptr(right), n, rows, cols,
-                                        C.byref(par), ptr(disp16), ptr(z),
-                                        torch.cuda.current_stream(dev).cuda_stream),
-              "erp_stereo_rows_dev")
+        call, name = ctx.L.erp_stereo_rows_dev, "erp_stereo_rows_dev"
+        if (int(n_paths), int(uniqueness)) != (4, 0):
+            par = capi.StereoParamsEx(par, int(n_paths), int(uniqueness))
+            call, name = ctx.L.erp_stereo_rows_ex_dev, "erp_stereo_rows_ex_dev"
+        check(call(ctx.h, ptr(left), ptr(right), n, rows, cols, C.byref(par), ptr(disp16), ptr(z),
+                   torch.cuda.current_stream(dev).cuda_stream), name)
         return (disp16, z) if depth else disp16
 
     @staticmethod
     def vertical(left_vertical, right_vertical, **kw):
         """disparity on the vertical views of erp_rotation.rectify_batch /
         PairBatchRunner.rectify_images ([P, W, H, 3]: W rows of H columns, the row index being
-        longitude): wrap_rows = 1."""
+        longitude): wrap_rows = 1.  The keywords are disparity's; with ``n_paths`` = 8 the
+        diagonal paths wrap their rows too, so every diagonal runs from pole to pole, and
+        ``uniqueness`` rejects the pixels whose best sum is not that much below the others."""
         if "wrap_rows" in kw:
             raise ValueError("vertical views wrap their rows; use disparity for wrap_rows = 0")
         return stereo.disparity(left_vertical, right_vertical, wrap_rows=1, **kw)

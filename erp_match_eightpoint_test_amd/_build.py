@@ -124,6 +124,7 @@ DRIVERS = {
     "guided": "guided_driver",       # erp::feature_matcher::match_guided
     "support": "support_driver",     # erp::eight_point::find_support
     "stereo": "stereo_driver",       # erp_stereo_rows_dev, the C ABI from C++
+    "stereo_ex": "stereo_ex_driver",  # erp_stereo_rows_ex_dev: eight paths and uniqueness
 }
 
 

@@ -206,7 +206,8 @@ EXPORTED = ["erp_ctx_create", "erp_ctx_destroy", "erp_status_string", "erp_ransa
             "erp_polish_winners_dev", "erp_pose_select_dev", "erp_eight_point_find_posed",
             "erp_match_guided_dev", "erp_match_guided", "erp_pair_batch_run_support",
             "erp_eight_point_find_support_dev", "erp_eight_point_find_support",
-            "erp_stereo_params_default", "erp_stereo_rows_dev"]
+            "erp_stereo_params_default", "erp_stereo_rows_dev",
+            "erp_stereo_params_ex_default", "erp_stereo_rows_ex_dev"]
 STAGES = ["knn2_filter", "knn2_merge", "bearings", "jump_prep", "sampler", "eigen",
           "valid_compact", "consensus_rows", "consensus_final", "consensus_bounds",
           "consensus_select", "windows", "gram", "knn2_candidates", "knn2_rescore",
@@ -247,6 +248,14 @@ STEREO_INVALID = -32768  # ERP_STEREO_INVALID
 class StereoParams(C.Structure):
     _fields_ = [("d_min", C.c_int32), ("n_disp", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32),
                 ("lr_max", C.c_int32), ("wrap_rows", C.c_int32), ("channels", C.c_int32)]
+
+
+class StereoParamsEx(C.Structure):  # erp_stereo_params_ex: rules 4b (n_paths) and 6b (uniqueness)
+    _fields_ = [("base", StereoParams), ("n_paths", C.c_int32), ("uniqueness", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+assert C.sizeof(StereoParams) == 28 and C.sizeof(StereoParamsEx) == 44
 
 
 class RectifyOutputs(C.Structure):
@@ -420,6 +429,10 @@ def load(build_if_missing: bool = False):
     L.erp_stereo_params_default.restype = None
     L.erp_stereo_rows_dev.argtypes = [P, P, P, C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(StereoParams), P, P, P]
+    L.erp_stereo_params_ex_default.argtypes = [C.POINTER(StereoParamsEx)]
+    L.erp_stereo_params_ex_default.restype = None
+    L.erp_stereo_rows_ex_dev.argtypes = [P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                         C.POINTER(StereoParamsEx), P, P, P]
     L.erp_stage_name.argtypes = [C.c_int32]
     L.erp_stage_name.restype = C.c_char_p
     L.erp_ctx_stage_times.argtypes = [P, P, P]

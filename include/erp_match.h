@@ -980,7 +980,7 @@ erp_status erp_rectify_results_dev(erp_ctx* ctx, const uint8_t* d_left, const ui
                                    const erp_pair_result* d_results, int32_t fill,
                                    const erp_rectify_outputs* outputs, void* stream);
 
-/* ---- dense stereo on row-rectified views: census + 4-path SGM (no reference counterpart) ----
+/* ---- dense stereo on row-rectified views: census + 4- or 8-path SGM (no reference counterpart) --
    The vertical views of erp_rectify_outputs are what this is for: rectify turns the baseline
    onto (0, -1, 0), the 89.999-degree turn about x puts both epipoles on the poles and the
    90-degree rotation makes every meridian -- one epipolar half-plane -- a row, so that a scene
@@ -1005,6 +1005,14 @@ erp_status erp_rectify_results_dev(erp_ctx* ctx, const uint8_t* d_left, const ui
         L_r(p,d) = c(p,d) + min(L_r(q,d), L_r(q,d-1) + p1, L_r(q,d+1) + p1, m + p2) - m,
       a neighbour d-1 or d+1 outside [0, D) left out.  S = the sum of the four L_r, uint16
       (L_r <= 63 + p2, so S <= 1272).
+   4b. The diagonal paths (erp_stereo_params_ex.n_paths == 8).  Four more paths r with the steps
+      (dy, dx) = (+1, +1), (-1, -1), (+1, -1), (-1, +1).  The previous pixel of p = (y, x) on
+      path r is q = (y - dy, x - dx).  When q's column is outside [0, cols), p is the first pixel
+      of its path: L_r = c.  When q's row is outside [0, rows): with wrap_rows == 1 the row is
+      taken modulo `rows` (any rows >= 1; at rows == 1 a diagonal is the row path), with
+      wrap_rows == 0 p is a first pixel.  Otherwise rule 4's recurrence, unchanged.  S = the sum
+      of all eight L_r, still uint16: S <= 8 * (63 + p2) = 2544.  The four paths of rule 4 still
+      do not wrap.
    5. Winner and sub-pixel.  d* = the first argmin over d of S(y,x,.).  a = S[d*-1],
       b = S[d*+1], c = S[d*], den = a + b - 2c.  off = 0 when d* is 0 or D-1 or den <= 0, else
       off = floor(((a - b)*16 + den) / (2*den)) (floor division on signed integers).
@@ -1013,6 +1021,9 @@ erp_status erp_rectify_results_dev(erp_ctx* ctx, const uint8_t* d_left, const ui
       S(y, xr + d_min + d, d) over the d whose column xr + d_min + d is in [0, cols).  Pixel
       (y,x) is invalid (ERP_STEREO_INVALID) when its xr = x - d_min - d* is outside [0, cols),
       or when lr_max >= 0 and abs(d* - dR(y,xr)) > lr_max.
+   6b. Uniqueness (erp_stereo_params_ex.uniqueness > 0), after rules 5 and 6.  Pixel (y,x) is
+      also invalid when some d with abs(d - d*) > 1 has
+      S(y,x,d) * (100 - uniqueness) < S(y,x,d*) * 100.  dR does not depend on it.
    7. Depth (optional), the left camera's, in units of |t|, meant for vertical views, where a
       row runs from pole to pole; the pixel-to-angle rule is the reference's pi * i / H
       (src/erp_rotation.cpp:68; no half-pixel offset).  thL = pi*x/cols,
@@ -1050,6 +1061,24 @@ erp_status erp_stereo_rows_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_
                                int32_t n_pairs, int32_t rows, int32_t cols,
                                const erp_stereo_params* params, int16_t* d_disp16,
                                float* d_depth, void* stream);
+/* The same call with rules 4b and 6b.  erp_stereo_params stays as it is; the extension carries
+   it.  With the defaults (4 paths, no uniqueness test) the output is erp_stereo_rows_dev's byte
+   for byte: that call is this one with them.  The scratch, the chunks and the S volume's size
+   are the same; the diagonal paths add two launches per chunk, the uniqueness test none.
+   Asynchronous and deterministic like erp_stereo_rows_dev.  Its argument checks, plus
+   ERP_INVALID_ARG before any launch for n_paths not 4 or 8, uniqueness outside 0..99 or a
+   non-zero reserved field. */
+typedef struct erp_stereo_params_ex {
+    erp_stereo_params base;
+    int32_t n_paths;      /* 4 or 8; default 4 */
+    int32_t uniqueness;   /* percent, 0..99; 0 disables; default 0 */
+    int32_t reserved[2];  /* must be 0 */
+} erp_stereo_params_ex;
+void erp_stereo_params_ex_default(erp_stereo_params_ex* p);   /* base = erp_stereo_params_default */
+erp_status erp_stereo_rows_ex_dev(erp_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right,
+                                  int32_t n_pairs, int32_t rows, int32_t cols,
+                                  const erp_stereo_params_ex* params, int16_t* d_disp16,
+                                  float* d_depth, void* stream);
 
 /* ---- SURF: feature_matcher::detect_key_point + comput_descriptor
    (src/feature_matcher.cpp:26-40) with xfeatures2d::SURF::create() defaults ---- */

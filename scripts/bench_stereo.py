@@ -1,11 +1,13 @@
 #!/usr/bin/env python
-"""The dense-stereo stage (erp_stereo_rows_dev) next to the call that
-feeds it.
+"""The dense-stereo stage (erp_stereo_rows_dev and erp_stereo_rows_ex_dev, DESIGN.md sections
+3.20 and 3.21) next to the call that feeds it.
 
 Per shape, in one process on one stream, HIP events, interleaved repetition by repetition:
   rectify   erp_rectify_batch_dev: the rectified and the vertical views of the P pairs;
   stereo    stereo.vertical on the vertical views where they lie, disp16 only;
-  stereo_z  the same with the depth.
+  stereo_z  the same with the depth;
+  stereo8   disp16 with n_paths = 8 (the diagonal paths, erp_stereo_rows_ex_dev);
+  stereo8_u the same with uniqueness = 15.
 Two shapes: one pair of 5376 x 2688 images (views of 5376 rows x 2688 columns) with D = 128, and
 8 pairs of 1344 x 672 with D = 64.  Images are bench_rectify's seeded device textures, the poses
 generic.  Median, min, max over --reps and spread = (max - min) / median; disp16 of the first and
@@ -14,7 +16,8 @@ the last repetition must be byte-identical: asserted.
 The S volume is rows * cols * D * 2 bytes per pair.  The kernels move, in volumes: paths along
 rows 3 (the forward walk stores, the backward walk loads and stores), paths along columns 4,
 winner 1 + (D - 1) / 1024 (each row once, plus the D - 1 columns to the left of every
-1024-column segment a second time): about 8.1 in all.
+1024-column segment a second time): about 8.1 in all.  With eight paths each of the two diagonal
+launches moves 4 more (both of its walks load and store): about 16.1.
 hbm_fraction = those volumes / time / 8 TB/s for the whole call; --kernel-stats CSV (the kernel
 statistics of a profiler run of this script, columns Name and TotalDurationNs or
 AverageNs + Calls) adds the time, volumes and bandwidth per kernel.  Writes one JSON document
@@ -42,6 +45,7 @@ WIN_SEGMENT = 1024  # csrc/stereo.hip kWinT
 def volumes(D):
     """S volumes each kernel moves, by a pattern of its name"""
     return {"stereo_path_kernel<*, false>": 3.0, "stereo_path_kernel<*, true>": 4.0,
+            "stereo_diag_kernel": 4.0,  # per launch; an eight-path call has two
             "stereo_winner_kernel": 1.0 + (D - 1) / WIN_SEGMENT}
 
 
@@ -65,8 +69,8 @@ def measure(name, shape, args):
     tv = rng.standard_normal((P, 3))
     tv = (tv / np.linalg.norm(tv, axis=1, keepdims=True)).astype(np.float32).astype(np.float64)
     kw = dict(d_min=-D // 2, n_disp=D, ctx=ctx)
-    t = {k: [] for k in ("rectify", "stereo", "stereo_z")}
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+    t = {k: [] for k in ("rectify", "stereo", "stereo_z", "stereo8", "stereo8_u")}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(10)]
     first = None
     for rep in range(-1, args.reps):  # (rep -1 warms every call and grows the scratch)
         ev[0].record()
@@ -79,18 +83,31 @@ def measure(name, shape, args):
         ev[4].record()
         disp_z, z = stereo.vertical(lv, rvv, depth=True, **kw)
         ev[5].record()
+        ev[6].record()
+        disp8 = stereo.vertical(lv, rvv, n_paths=8, **kw)
+        ev[7].record()
+        ev[8].record()
+        disp8_u = stereo.vertical(lv, rvv, n_paths=8, uniqueness=15, **kw)
+        ev[9].record()
         torch.cuda.synchronize()
         if first is None:
-            first = disp.clone()
+            first, first8 = disp.clone(), disp8.clone()
         if rep < 0:
             continue
-        for k, i in (("rectify", 0), ("stereo", 2), ("stereo_z", 4)):
+        for k, i in (("rectify", 0), ("stereo", 2), ("stereo_z", 4), ("stereo8", 6),
+                     ("stereo8_u", 8)):
             t[k].append(ev[i].elapsed_time(ev[i + 1]))
     assert torch.equal(first, disp) and torch.equal(first, disp_z), f"{name}: disp16 differs"
+    assert torch.equal(first8, disp8), f"{name}: eight-path disp16 differs"
+    kept = disp8 != capi.STEREO_INVALID
+    assert bool((disp8_u[kept] == disp8[kept]).logical_or(disp8_u[kept] == capi.STEREO_INVALID).all())
     vol = float(W) * H * D * 2
     med = float(np.median(t["stereo"]))
     valid = disp != capi.STEREO_INVALID
-    nvol = sum(volumes(D).values())
+    vols = volumes(D)
+    nvol = sum(v for k, v in vols.items() if "diag" not in k)
+    nvol8 = nvol + 2 * vols["stereo_diag_kernel"]
+    med8 = float(np.median(t["stereo8"]))
     doc = {"shape": name, **shape, "rows": W, "cols": H, "d_min": kw["d_min"], "reps": args.reps,
            "s_volume_bytes_per_pair": vol,
            "chunk_pairs": max(1, min(P, int((ctx.get_option("stereo_chunk_mb") << 20) // vol))),
@@ -100,10 +117,17 @@ def measure(name, shape, args):
            "volumes_moved": nvol, "bytes_moved": nvol * vol * P,
            "hbm_bytes_per_s": nvol * vol * P / (med * 1e-3),
            "hbm_fraction": nvol * vol * P / (med * 1e-3) / HBM_BYTES_PER_S,
+           "stereo8_over_stereo": med8 / med,
+           "volumes_moved_8": nvol8,
+           "hbm_bytes_per_s_8": nvol8 * vol * P / (med8 * 1e-3),
+           "hbm_fraction_8": nvol8 * vol * P / (med8 * 1e-3) / HBM_BYTES_PER_S,
            "valid_fraction": float(valid.float().mean()),
+           "valid_fraction_8": float(kept.float().mean()),
+           "valid_fraction_8_u15": float((disp8_u != capi.STEREO_INVALID).float().mean()),
+           "disp16_changed_by_8_paths": float((disp8 != disp).float().mean()),
            "finite_depth_fraction": float(torch.isfinite(z).float().mean()),
            "disp16_identical": True}
-    del lefts, rights, out, disp, disp_z, z
+    del lefts, rights, out, disp, disp_z, z, disp8, disp8_u
     torch.cuda.empty_cache()
     return doc
 
@@ -124,7 +148,8 @@ def kernel_table(path, shape):
         for pat, v in volumes(shape["D"]).items():
             head, _, tail = pat.partition("*")
             if head in n and tail in n:
-                # the chunks of a call share the kernel: calls per stereo call = chunks
+                # the chunks of a call share the kernel: calls per stereo call = chunks (the
+                # diagonal kernel: two launches per chunk, 4 volumes each)
                 row["volumes"] = v
                 row["hbm_bytes_per_s"] = v * vol / shape["chunks"] / (ms * 1e-3)
                 row["hbm_fraction"] = row["hbm_bytes_per_s"] / HBM_BYTES_PER_S
@@ -139,7 +164,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--kernel-stats", dest="kernel_stats", default=None,
                     help="kernel statistics CSV of a profiler run of ONE shape (--shapes)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r21a_bench_stereo.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r22a_bench_stereo.json"))
     args = ap.parse_args()
     names = args.shapes.split(",")
     if args.kernel_stats:
